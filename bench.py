@@ -1,7 +1,15 @@
 """Headline benchmark: env-steps/s of the batched assignment-env rollout on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 0..4] [--selector eps|sap|random]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU, RCCL)
+
+A plain run sets up the workload, warms up, times the K steps and prints the result line
+(value, ms_per_step, and the roofline / kernels_ms figures read off the timed steps' own HIP
+events).  --dump-outputs DIR then also writes what the last timed step computed (dump_outputs).
+Everything that takes runs of its own -- the CPU baselines, the secondary legs, roofline_agent
+(from the split-schedule leg) -- runs under --full only.  (--selector sap|bids: one selection
+after the timed steps counts the augmenting-path steps for roofline_lsa.)
 
 --config i selects BASELINE.json configs[i] (default 2; 3 is configs[2] per GPU on N GPUs):
   0  4 x 4, 1 env, fused RNN agent + epsilon-greedy  (the reference's CPU plumbing case)
@@ -30,14 +38,14 @@ The JSON line also carries:
                   (profiles/*pmc_rollout_kernel*.json), `issue` = its SQ figures, `bound` derived
                   from them (HBM or the store-ordered latency).  On the split schedule: the env
                   step kernel (SURVEY §8(d)'s B_step * E).
-  roofline_agent  the agent kernel (split-schedule leg) against its MFMA roof and HBM.
+  roofline_agent  the agent kernel (split-schedule leg, --full) against its MFMA roof and HBM.
   kernels_ms      per-step kernel times (fused rollout / env step / selection).
-  cpu_baseline    rank 0 at N = 1 only: the reference's CPU design (subprocess-per-env
+  cpu_baseline    --full, rank 0 at N = 1 only: the reference's CPU design (subprocess-per-env
                   ParallelRunner + numpy env + CPU RNN agent, oracle/cpu_parallel_runner.py) on
                   a bounded sample of the same workload: step-loop-only and reset-amortised
                   rates, the worker count used and the host's core count.
-  secondary       (N = 1, --secondary 1, the default then; each leg with its own value and
-                  ms_per_step): split_rollout (separate launches), step_rollout (one fused
+  secondary       (--full at N = 1, --secondary 1, the default then; each leg with its own value
+                  and ms_per_step): split_rollout (separate launches), step_rollout (one fused
                   launch per step), pytorch_agent (configs[2] read literally: the PyTorch
                   RNNAgent + asg_epsilon_greedy), sap (fused noise + LSA per env, roofline_lsa
                   against both issue bounds), iql / reda (the reference's mock algorithms:
@@ -357,12 +365,19 @@ def parse(argv=None):
     p.add_argument("--agent", default=None, choices=["rnn", "rnn_fused", "rnn_torch"],
                    help="rnn (the reference's name; default): the RNNAgent with its inference forward as one HIP "
                         "kernel wherever the shape allows (= rnn_fused); rnn_torch: the plain PyTorch module")
-    p.add_argument("--cpu-baseline", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baselines (--cpu-baseline), the "
+                        "secondary legs (--secondary, --real-envs)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last of them computed (a fixed, seeded sample of "
+                        "envs) as DIR/<name>.npy")
+    p.add_argument("--cpu-baseline", type=int, default=1, help="with --full: 0 skips the CPU baselines")
     p.add_argument("--cpu-episodes", type=int, default=2, help="minimum CPU-baseline episodes")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline sample length (s)")
     p.add_argument("--cpu-workers", type=int, default=None,
                    help=f"CPU-baseline env workers (default min(os.cpu_count(), {CPU_WORKER_CAP}))")
-    p.add_argument("--secondary", type=int, default=-1, help="secondary legs (-1: on at N = 1 for configs 2/3)")
+    p.add_argument("--secondary", type=int, default=-1,
+                   help="with --full: secondary legs (-1: on at N = 1 for configs 2/3)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--fused-rollout", type=int, default=1, choices=[0, 1, 2, 3],
                    help="1 (default): the whole episode -- env steps + agent/eps-greedy selections -- in one kernel "
@@ -446,8 +461,41 @@ def cpu_baseline(a):
                                                      f"(oracle/asg_rollout.c), no agent network"}}
 
 
+DUMP_BUDGET = 48 << 20  # bytes of --dump-outputs files (float32 / float64 values)
+
+
+def dump_outputs(out_dir, batch, env, mac, t, next_selected, seed):
+    """Write what the timed path's last step (episode step t) left for its caller, as
+    out_dir/<name>.npy: the batch rows it read and wrote -- row t's actions, actions_onehot,
+    rewards and terminated, row t + 1's obs, avail_actions, prev_assigns and beta, and, when the
+    step also selected for row t + 1, that row's actions (next_actions) -- and the agent's
+    hidden state after it, each for a fixed sample of envs (env_index, drawn from `seed`; every
+    env when they fit DUMP_BUDGET), plus every env's episode return so far (returns).  float32,
+    but float64 for returns and env_index."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    td = batch.data.transition_data
+    E = batch.batch_size
+    rows = {k: (td[k], t) for k in ("actions", "actions_onehot", "rewards", "terminated") if k in td}
+    rows.update({k: (td[k], t + 1) for k in ("obs", "avail_actions", "prev_assigns", "beta") if k in td})
+    if next_selected:
+        rows["next_actions"] = (td["actions"], t + 1)
+    h = getattr(mac, "hidden_states", None)
+    h = h.reshape(E, -1) if torch.is_tensor(h) and h.numel() and h.numel() % E == 0 else None
+    per_env = 4 * (sum(v[:1, 0].numel() for v, _ in rows.values()) + (h.shape[1] if h is not None else 0))
+    idx = np.sort(np.random.RandomState(seed).permutation(E)[:max(1, min(E, DUMP_BUDGET // per_env))])
+    ix = torch.as_tensor(idx, device=td["obs"].device)
+    out = {k: v[ix, r].to(torch.float32) for k, (v, r) in rows.items()}
+    if h is not None:
+        out["hidden_states"] = h[ix].to(torch.float32)
+    out["returns"] = env.get_returns().to(torch.float64)
+    out["env_index"] = torch.as_tensor(idx.astype(np.float64))
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.cpu().numpy())
+
+
 def run_leg(a, dev, world, E, steps, warmup, selector=None, agent=None, count_lsa=False, fused=None, mac="basic_mac",
-            use_rnn=None, **extra):
+            use_rnn=None, dump_dir=None, **extra):
     """Build runner + MAC for one workload and time `steps` transitions after `warmup`.
     Returns elapsed seconds (max over ranks) and mean HIP-event times of the env step, the
     whole selection, and (SAP) the selector kernel alone."""
@@ -627,6 +675,9 @@ def run_leg(a, dev, world, E, steps, warmup, selector=None, agent=None, count_ls
     asg_dist.barrier()
     elapsed = time.perf_counter() - t0
     state["timing"] = False
+    if dump_dir:
+        next_selected = state["selected"] or (state.get("mode") == "episode" and state["t"] < a.T)
+        dump_outputs(dump_dir, runner.batch, env, mac, state["t"] - 1, next_selected, a.seed)
     if runner.env.k == a.T:
         runner.finish_episode(sync=False)
     runner.flush_pending()  # surfaces any sticky device error of the timed steps
@@ -857,13 +908,14 @@ def main():
     from marl_sap_amd import dist as asg_dist
     rank, world = asg_dist.init_from_env()
     # CPU baseline first: its worker processes are forked before this process touches the GPU
-    cpu = cpu_baseline(a) if rank == 0 and world == 1 and a.cpu_baseline else None
+    cpu = cpu_baseline(a) if a.full and rank == 0 and world == 1 and a.cpu_baseline else None
 
     local = asg_dist.local_device_index()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     E = a.envs
-    res = run_leg(a, dev, world, E, a.steps, a.warmup, count_lsa=True)
+    res = run_leg(a, dev, world, E, a.steps, a.warmup, count_lsa=True,
+                  dump_dir=a.dump_outputs if rank == 0 else None)
     G = res["global_envs"]
     value = G * a.steps / res["elapsed"]
     kern_ms, sel_ms = res["kern_ms"], res["sel_ms"]
@@ -882,7 +934,7 @@ def main():
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pm.get("hbm_bytes_per_launch") if pm else None,
                 "kernel": "asg::step_kernel", "kernel_ms": round(kern_ms, 4), "bytes_per_launch": per_launch}
 
-    secondary = a.secondary if a.secondary >= 0 else int(world == 1 and a.config in (2, 3))
+    secondary = a.full and (a.secondary if a.secondary >= 0 else int(world == 1 and a.config in (2, 3)))
     extra = {}
 
     def leg_base(r, sk, sw):
@@ -1141,6 +1193,7 @@ def main():
             "metric": f"env steps/sec (whole node), {a.n}-agent assignment env, 1/2/4/8 MI355X",
             "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": round(res["elapsed"] / a.steps * 1e3, 4), "higher_is_better": True,
+            "full": bool(a.full),
             "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": f"synthetic (Philox {a.benefits} benefits, random-init RNN agent)",
             "config": {"workload": CONFIGS[a.config]["label"] + f"; T={a.T}, L={a.L}, BasicMAC+{a.agent}"

@@ -172,6 +172,15 @@ def test_bench_accounting():
     assert bench.agent_peak(64, 64, 3, 1) == pytest.approx(81920 / (32768 / 157.3 + 49152 / (2500 / 6)))
 
 
+def test_bench_plain_and_full_options():
+    """A plain run asks for nothing beyond the headline leg; --full and --dump-outputs are opt-in."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out" and a.cpu_baseline == 1 and a.secondary == -1
+
+
 def test_bench_profile_order_and_reset_share(monkeypatch):
     """pmc_lookup takes the newest summary by (round, session) -- s10 after s9 -- and the
     fused roofline's PMC traffic carries the same reset share as its bytes_per_launch."""

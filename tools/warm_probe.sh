@@ -12,7 +12,7 @@ d = json.loads([l for l in open('$OUT/$name.json') if l.startswith('{')][-1]); k
 print('$name', d['steps'], d['warmup'], d['value'], d['ms_per_step'], k.get('fused_rollout_per_step'))"
 }
 for rep in 1 2; do
-  run driver_cmd --steps 20 --warmup 5
+  run driver_cmd --full --steps 20 --warmup 5
   run no_cpu --cpu-baseline 0 --steps 20 --warmup 5
   run long --cpu-baseline 0 --steps 60 --warmup 20
 done
