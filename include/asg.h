@@ -37,6 +37,9 @@
  *                              (action_selectors/classic_selectors.py:28-54)
  *   asg_rnn_agent_forward      RNNAgent.forward (modules/agents/rnn_agent.py:23-31) as called by
  *                              BasicMAC.forward for action selection (basic_controller.py:26-48)
+ *   asg_rnn_agent_unroll       the learner's loop of BasicMAC.forward over the T + 1 rows of a
+ *                              sampled batch (learners/sap_q_learner.py:69-84) in one launch;
+ *                              asg_rnn_agent_unroll_backward = autograd's walk back through it
  *   asg_get_returns            the runners' episode_return accumulation
  *                              (episode_runner.py:84, parallel_runner.py:173-176)
  *   asg_filtered_*             FilteredSAPActionSelector / FilteredEpsGrSAPTestActionSelector
@@ -316,6 +319,44 @@ int asg_rnn_agent_select(const float *x, int64_t x_stride, int64_t R, int K, con
                          const int64_t avail_strides[2], int n, double epsilon, uint64_t seed,
                          uint64_t counter, int64_t env_index_base, int64_t *out,
                          const int64_t out_strides[2], int32_t *status, void *hip_stream);
+
+/* ---- the GRU agent unrolled over time (the learner's two unrolls and their backward) -------
+ * asg_rnn_agent_unroll: T1 successive RNNAgent.forward calls (learners/sap_q_learner.py:69-84)
+ * in one launch; each wave keeps its rows' hidden state on chip across all steps.
+ * x: element strides x_strides = {t, env, agent}, K contiguous; row r = env * n + agent,
+ * R = B * n rows (a batch-major ReplayBuffer sample and the time-major runner batch both fit,
+ * with no copy; float4 loads when K % 4 == 0 and x and its strides are 16-B aligned).
+ * h0 [R][64] with row stride h_stride (% 4 == 0; 0 = one row broadcast, NULL = zeros).
+ * Weights in the torch layouts, contiguous: W1 [64][K], W_ih / W_hh [192][64], W2 [n_out][64],
+ * b1 [64], b_ih / b_hh [192], b2 [n_out].  Outputs, contiguous: q [T1][R][n_out],
+ * h_all [T1][R][64] and, when save is not NULL, save [5][T1][R][64]: the planes
+ * x1 = relu(fc1), r, z, n and gh_n = W_hn h + b_hn of every step, for the backward pass.
+ * ASG_E_INVALID_ARG before any device call when hidden != 64, use_rnn = 0, n_out outside
+ * 1..512, T1 < 1, B * n < 1, K < 1 or a pointer is misaligned. */
+int asg_rnn_agent_unroll(const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
+                         const float *h0, int64_t h_stride, const float *W1, const float *W_ih,
+                         const float *W_hh, const float *W2, const float *b1, const float *b_ih,
+                         const float *b_hh, const float *b2, int hidden, int n_out, int use_rnn, float *q,
+                         float *h_all, float *save, void *hip_stream);
+/* The sequential core of backpropagation through that unroll.  dh_q [T1][R][64] is the
+ * gradient reaching each h_t through fc2 (dQ_t @ W2), dh_last [R][64] (may be NULL) the one on
+ * the final hidden state; save / h_all / h0 as asg_rnn_agent_unroll wrote and read them.
+ * Walking t = T1-1 .. 0 with dh starting from dh_last and h_{t-1} = h0 at t = 0:
+ *     dh += dh_q[t]
+ *     dn = dh (1 - z);  dz = dh (h_{t-1} - n);  dn_pre = dn (1 - n^2)
+ *     dr_pre = dn_pre gh_n r (1 - r);  dz_pre = dz z (1 - z)
+ *     dgi[t] = [dr_pre, dz_pre, dn_pre];  dgh[t] = [dr_pre, dz_pre, dn_pre r]
+ *     dx1[t] = (dgi[t] @ W_ih) (x1[t] > 0);  dh = dh z + dgh[t] @ W_hh
+ * Outputs: dgi [T1][R][192], dgh_n [T1][R][64] (the n part of dgh; its r and z parts are
+ * dgi's), dx1 [T1][R][64] and, when not NULL, dh0 [R][64].  Exact f32 MFMA products in a fixed
+ * order, no atomics: the same inputs give the same bits.  The parameter gradients are GEMMs
+ * over the T1 * R rows (dW_ih = dgi^T x1, dW_hh = dgh^T h_prev, dW1 = dx1^T x, ...) left to
+ * the caller.  Same argument checks as asg_rnn_agent_unroll. */
+int asg_rnn_agent_unroll_backward(const float *dh_q, const float *dh_last, const float *save,
+                                  const float *h_all, const float *h0, int64_t h_stride,
+                                  const float *W_ih, const float *W_hh, int T1, int64_t R, int hidden,
+                                  int n_out, int use_rnn, float *dgi, float *dgh_n, float *dx1, float *dh0,
+                                  void *hip_stream);
 
 /* ---- filtered selectors (the real-env algorithms' action_selector) -------------------------
  * The agent emits M + 1 values per agent: its top-M tasks by total benefit and a baseline.

@@ -192,6 +192,32 @@ class BasicMAC:
             agent_outs = torch.nn.functional.softmax(agent_outs, dim=-1)
         return agent_outs.view(ep_batch.batch_size, self.n, -1)
 
+    def forward_sequence(self, ep_batch):
+        """forward() over every row of the batch, as the learners call it (reference
+        learners/sap_q_learner.py:69-84): init_hidden, then t = 0 .. max_seq_length - 1.
+        Returns [B, T1, n, n_out] and leaves hidden_states as those calls would.  The agent's
+        unroll() runs the sequence (one launch for the fused GRU agent)."""
+        bs = ep_batch.batch_size
+        self.init_hidden(bs)
+        agent_outs, self.hidden_states = self.agent.unroll(self._build_sequence_inputs(ep_batch), None)
+        if self.agent_output_type == "pi_logits":
+            agent_outs = torch.nn.functional.softmax(agent_outs, dim=-1)
+        return agent_outs
+
+    def _build_sequence_inputs(self, batch):
+        """_build_inputs for all rows at once: [B, T1, n, K]; the plain observation stays a
+        view of the batch (batch- or time-major)."""
+        bs, T1 = batch.batch_size, batch.max_seq_length
+        inputs = [batch["obs"].float()]
+        if self.args.obs_last_action:
+            onehot = batch["actions_onehot"]
+            inputs.append(torch.cat([torch.zeros_like(onehot[:, :1]), onehot[:, :-1]], dim=1))
+        if self.args.obs_agent_id:
+            inputs.append(torch.eye(self.n, device=batch.device).view(1, 1, self.n, self.n).expand(bs, T1, -1, -1))
+        if len(inputs) == 1:
+            return inputs[0].reshape(bs, T1, self.n, -1)
+        return torch.cat([x.reshape(bs, T1, self.n, -1).to(torch.float32) for x in inputs], dim=3)
+
     def init_hidden(self, batch_size):
         self.hidden_states = self.agent.init_hidden().unsqueeze(0).expand(batch_size, self.n, -1)
 

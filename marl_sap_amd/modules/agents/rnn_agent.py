@@ -34,13 +34,109 @@ class RNNAgent(nn.Module):
         q = self.fc2(h)
         return q, h
 
+    def unroll(self, x, h0=None):
+        """The agent over a whole sequence: x [B, T1, n, K] -> (q [B, T1, n, n_out], h_last
+        [B * n, hidden]), T1 successive forward calls starting from h0 (None: zeros), the
+        loop the reference learner runs (learners/sap_q_learner.py:69-84)."""
+        return self._unroll_loop(x, h0)
+
+    def _unroll_loop(self, x, h0=None):
+        B, T1, n, K = x.shape
+        H = self.args.hidden_dim
+        h = self.init_hidden().expand(B * n, H) if h0 is None else h0.reshape(-1, H)
+        qs = []
+        for t in range(T1):
+            q, h = self.forward(x[:, t].reshape(B * n, K), h)
+            qs.append(q.view(B, n, -1))
+        return torch.stack(qs, dim=1), h
+
+
+class _GRUUnroll(torch.autograd.Function):
+    """asg_rnn_agent_unroll under autograd: the forward kernel saves x1, r, z, n and gh_n per
+    step, asg_rnn_agent_unroll_backward walks the recurrence back, and the parameter
+    gradients are GEMMs over the flattened T1 * R rows."""
+
+    @staticmethod
+    def forward(ctx, x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2):
+        q, h_all, save = _unroll_launch(x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2, True)
+        ctx.save_for_backward(x, h0, W1, Wih, Whh, W2, h_all, save)
+        B, T1, n, _ = x.shape
+        return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
+
+    @staticmethod
+    def backward(ctx, dq, dh_last):
+        x, h0, W1, Wih, Whh, W2, h_all, save = ctx.saved_tensors
+        B, T1, n, K = x.shape
+        R, H, n_out = B * n, Wih.shape[1], W2.shape[0]
+        N = T1 * R
+        dev = x.device
+        if dq is None:
+            dQ = torch.zeros((N, n_out), dtype=torch.float32, device=dev)
+        else:
+            dQ = dq.permute(1, 0, 2, 3).reshape(N, n_out).float().contiguous()
+        if dh_last is not None:
+            dh_last = dh_last.reshape(R, H).float().contiguous()
+        dh_q = dQ @ W2
+        dgi = torch.empty((N, 3 * H), dtype=torch.float32, device=dev)
+        dgh_n = torch.empty((N, H), dtype=torch.float32, device=dev)
+        dx1 = torch.empty((N, H), dtype=torch.float32, device=dev)
+        dh0 = torch.empty((R, H), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        h0k, hs = _h0_arg(h0, R, H)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().asg_rnn_agent_unroll_backward(
+                p(dh_q), p(dh_last), p(save), p(h_all), p(h0k), hs, p(Wih), p(Whh), T1, R, H, n_out, 1, p(dgi),
+                p(dgh_n), p(dx1), p(dh0), _lib.stream_ptr(dev)))
+        hf = h_all.view(N, H)
+        if h0k is None:
+            h_first = torch.zeros((R, H), dtype=torch.float32, device=dev)
+        else:
+            h_first = h0k.expand(R, H) if hs == 0 else h0k
+        h_prev = torch.cat([h_first, hf[:N - R]], dim=0)
+        dgh = torch.cat([dgi[:, :2 * H], dgh_n], dim=1)
+        xf = x.permute(1, 0, 2, 3).reshape(N, K)
+        if dh0 is not None and h0 is not None:
+            dh0 = dh0.sum(0, keepdim=True).view(h0.shape) if hs == 0 else dh0.view(h0.shape)
+        return (None, dh0, dx1.t() @ xf, dx1.sum(0), dgi.t() @ save[0].view(N, H), dgh.t() @ h_prev, dgi.sum(0),
+                dgh.sum(0), dQ.t() @ hf, dQ.sum(0))
+
+
+def _h0_arg(h0, R, H):
+    """h0 as the kernels take it: ([rows, H] tensor or None, row stride; 0 = one row broadcast)."""
+    if h0 is None:
+        return None, 0
+    if h0.numel() == H:
+        return h0.reshape(1, H).float().contiguous(), 0
+    h = h0.reshape(R, H)
+    if h.dtype != torch.float32 or h.stride(-1) != 1 or h.stride(0) % 4 != 0 or h.data_ptr() % 16 != 0:
+        h = h.float().contiguous()
+    return h, h.stride(0)
+
+
+def _unroll_launch(x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2, save):
+    B, T1, n, K = x.shape
+    R, H, n_out = B * n, Wih.shape[1], W2.shape[0]
+    dev = x.device
+    q = torch.empty((T1, R, n_out), dtype=torch.float32, device=dev)
+    h_all = torch.empty((T1, R, H), dtype=torch.float32, device=dev)
+    sv = torch.empty((5, T1, R, H), dtype=torch.float32, device=dev) if save else None
+    h0k, hs = _h0_arg(h0, R, H)
+    ws = [t.detach().contiguous() for t in (W1, Wih, Whh, W2, b1, bih, bhh, b2)]
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().asg_rnn_agent_unroll(
+            p(x), _lib.i64arr([x.stride(1), x.stride(0), x.stride(2)]), T1, B, n, K, p(h0k), hs, *[p(w) for w in ws],
+            H, n_out, 1, p(q), p(h_all), p(sv), _lib.stream_ptr(dev)))
+    return q, h_all, sv
+
 
 class RNNFusedAgent(RNNAgent):
     """RNNAgent with the same parameters / state_dict, whose inference forward (no autograd:
     the rollout's action selection) is one fused HIP kernel (asg_rnn_agent_forward: f32
     MFMA, fc1 + GRUCell + fc2 with every intermediate in registers; hidden 64, any input
     size, n_out = m up to 512 -- the real envs' m = 450 included).  With autograd enabled
-    (learner training) it is the plain PyTorch module, so gradients are unchanged."""
+    (learner training) it is the plain PyTorch module, so gradients are unchanged.  unroll()
+    runs a whole sequence, and its backward pass, in one launch each (asg_unroll.hip)."""
 
     def __init__(self, input_shape, args, n_out=None):
         super().__init__(input_shape, args, n_out)
@@ -126,6 +222,26 @@ class RNNFusedAgent(RNNAgent):
         return [p(self._packed(K, device)), p(self.fc1.bias), p(self.rnn.bias_ih if rnn else self.rnn.bias),
                 p(self.rnn.bias_hh) if rnn else None, p(self.fc2.bias), int(K), int(H), int(rnn), p(h), int(hs),
                 h_out]
+
+    def unroll(self, x, h0=None):
+        """x [B, T1, n, K] (any batch / time / agent strides, contiguous K) -> (q [B, T1, n,
+        n_out], h_last [B * n, hidden]).  The GRU agent on the GPU runs the whole sequence
+        in one launch (asg_rnn_agent_unroll; under autograd with its one-launch backward,
+        asg_rnn_agent_unroll_backward, differentiable in the eight parameter tensors and h0); the
+        Linear agent and CPU tensors loop the module over t, as does args.unfused_unroll = True
+        (the A/B switch of tools/bench_learner.py)."""
+        if not (self.args.use_rnn and x.is_cuda and x.dim() == 4) or getattr(self.args, "unfused_unroll", False):
+            return self._unroll_loop(x, h0)
+        if x.dtype != torch.float32 or x.stride(-1) != 1:
+            x = x.float().contiguous()
+        x = x.detach()  # observations are data: no gradient flows into them
+        B, T1, n, _ = x.shape
+        ps = (self.fc1.weight, self.fc1.bias, self.rnn.weight_ih, self.rnn.weight_hh, self.rnn.bias_ih,
+              self.rnn.bias_hh, self.fc2.weight, self.fc2.bias)
+        if torch.is_grad_enabled() and (any(w.requires_grad for w in ps) or (h0 is not None and h0.requires_grad)):
+            return _GRUUnroll.apply(x, h0, *ps)
+        q, h_all, _ = _unroll_launch(x, h0, *ps, False)
+        return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
 
     def _packed(self, K, device):
         """Weights in the kernel's fragment order, re-packed only when a weight changed

@@ -1,0 +1,138 @@
+"""RNNFusedAgent.unroll (asg_rnn_agent_unroll / asg_rnn_agent_unroll_backward: the GRU agent
+over a whole sequence in one launch each way) against the PyTorch module looped over t in
+float64 (the loop of learners/sap_q_learner.py:69-84).  Tolerance: the rule of
+tests/test_gpu_agent.py -- the kernels' max error against float64 may be at most 4 x the
+fp32 PyTorch autograd path's own error on the same inputs, plus 1e-7 max|reference|."""
+from types import SimpleNamespace
+
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+if not torch.cuda.is_available():
+    pytest.skip("needs a ROCm GPU", allow_module_level=True)
+
+from marl_sap_amd.modules.agents import RNNAgent, RNNFusedAgent  # noqa: E402
+
+DEV = torch.device("cuda", 0)
+NAMES = ["fc1.weight", "fc1.bias", "rnn.weight_ih", "rnn.weight_hh", "rnn.bias_ih", "rnn.bias_hh", "fc2.weight",
+         "fc2.bias"]
+# (T1, B, n, K, n_out): a single step below one tile; several steps at that ragged R; R ragged
+# across waves with K % 4 != 0; the aligned split-f16 shape; n_out > 256; the workload's depth
+SHAPES = [(1, 3, 5, 20, 7), (4, 3, 5, 20, 7), (5, 2, 37, 70, 20), (3, 4, 16, 256, 64), (2, 1, 20, 490, 450),
+          (21, 2, 8, 64, 16)]
+
+
+def _loop(agent, x, h0):
+    """T1 successive RNNAgent.forward calls (the PyTorch module, any dtype)."""
+    B, T1, n, K = x.shape
+    h = torch.zeros((B * n, 64), dtype=x.dtype, device=x.device) if h0 is None else h0
+    qs = []
+    for t in range(T1):
+        q, h = RNNAgent.forward(agent, x[:, t].reshape(B * n, K), h)
+        qs.append(q.view(B, n, -1))
+    return torch.stack(qs, 1), h
+
+
+def _make(T1, B, n, K, m, time_major, dense_h0, seed):
+    torch.manual_seed(seed)
+    args = SimpleNamespace(hidden_dim=64, use_rnn=True, m=m)
+    ref = RNNAgent(K, args).to(DEV)
+    fused = RNNFusedAgent(K, args).to(DEV)
+    fused.load_state_dict(ref.state_dict())
+    ref64 = RNNAgent(K, args).to(DEV).double()
+    ref64.load_state_dict({k: v.double() for k, v in ref.state_dict().items()})
+    if time_major:  # the runner batch: [T1][B] storage seen as [B, T1, ...]
+        x = torch.randn((T1, B, n, K), device=DEV).transpose(0, 1)
+    else:
+        x = torch.randn((B, T1, n, K), device=DEV)
+    h0 = torch.randn((B * n, 64), device=DEV) * 0.5 if dense_h0 else None
+    wq = torch.randn((B, T1, n, m), device=DEV)  # the loss: random weights on q and h_last
+    wh = torch.randn((B * n, 64), device=DEV)
+    return ref, fused, ref64, x, h0, wq, wh
+
+
+def _run(fn, agent, x, h0, wq, wh):
+    """(q, h_last, grads of the eight parameter tensors [+ h0]) of loss = <q, wq> + <h_last, wh>."""
+    agent.zero_grad()
+    h = None if h0 is None else h0.clone().requires_grad_(True)
+    q, h_last = fn(agent, x, h)
+    ((q * wq).sum() + (h_last * wh).sum()).backward()
+    sd = dict(agent.named_parameters())
+    grads = {k: sd[k].grad.clone() for k in NAMES}
+    if h is not None:
+        grads["h0"] = h.grad.clone()
+    return q.detach(), h_last.detach(), grads
+
+
+@pytest.mark.parametrize("dense_h0", [False, True])
+@pytest.mark.parametrize("time_major", [False, True])
+@pytest.mark.parametrize("T1,B,n,K,m", SHAPES)
+def test_unroll_forward_and_gradients_match_float64(T1, B, n, K, m, time_major, dense_h0):
+    ref, fused, ref64, x, h0, wq, wh = _make(T1, B, n, K, m, time_major, dense_h0, T1 * 100 + K)
+    d = lambda t: None if t is None else t.double()  # noqa: E731
+    q64, h64, g64 = _run(_loop, ref64, x.double(), d(h0), wq.double(), wh.double())
+    q32, h32, g32 = _run(_loop, ref, x, h0, wq, wh)
+    unroll = lambda a, xx, hh: a.unroll(xx, hh)  # noqa: E731
+    qf, hf, gf = _run(unroll, fused, x, h0, wq, wh)
+    assert qf.shape == (B, T1, n, m) and hf.shape == (B * n, 64)
+    assert set(gf) == set(g64) and len(gf) == 8 + int(dense_h0)
+    items = [("q", qf, q32, q64), ("h_last", hf, h32, h64)] + [(k, gf[k], g32[k], g64[k]) for k in g64]
+    for name, got, base, want in items:
+        assert got.shape == want.shape, name
+        err_fused = (got.double() - want).abs().max().item()
+        err_torch = (base.double() - want).abs().max().item()
+        floor = 1e-7 * want.abs().max().item()
+        print(f"{name}: max |err| vs float64: fused {err_fused:.3e}, torch fp32 {err_torch:.3e}, floor {floor:.1e}")
+        assert err_fused <= 4 * err_torch + floor, (name, err_fused, err_torch, floor)
+    # a second run on the same inputs: identical bits (no floating-point atomics)
+    qf2, hf2, gf2 = _run(unroll, fused, x, h0, wq, wh)
+    assert torch.equal(qf2, qf) and torch.equal(hf2, hf)
+    for k in gf:
+        assert torch.equal(gf2[k], gf[k]), k
+
+
+@pytest.mark.parametrize("T1,B,n,K,m", SHAPES)
+def test_no_grad_unroll_matches_successive_forward_calls(T1, B, n, K, m):
+    _, fused, _, x, h0, _, _ = _make(T1, B, n, K, m, True, True, 7 + K)
+    with torch.no_grad():
+        for h_start in (None, h0):
+            q, h_last = fused.unroll(x, h_start)
+            h = fused.init_hidden().expand(B * n, 64) if h_start is None else h_start
+            qs = []
+            for t in range(T1):
+                qt, h = fused(x[:, t].reshape(B * n, K), h)  # asg_rnn_agent_forward
+                qs.append(qt.view(B, n, m))
+            assert not q.requires_grad
+            torch.testing.assert_close(q, torch.stack(qs, 1), rtol=1e-5, atol=2e-5)
+            torch.testing.assert_close(h_last, h, rtol=1e-5, atol=2e-5)
+
+
+def test_unroll_with_only_h_last_used_and_broadcast_h0():
+    """Gradients when q is unused, and a one-row h0 broadcast to all rows (stride 0)."""
+    ref, fused, _, x, _, _, wh = _make(3, 2, 9, 24, 5, False, False, 3)
+    for agent, fn in ((ref, _loop), (fused, lambda a, xx, hh: a.unroll(xx, hh))):
+        agent.zero_grad()
+        h0 = (torch.arange(64, device=DEV, dtype=torch.float32) / 64 - 0.5).view(1, 64).requires_grad_(True)
+        q, h_last = fn(agent, x, h0.expand(18, 64) if agent is ref else h0)
+        (h_last * wh).sum().backward()
+        if agent is ref:  # fc2 takes no part: autograd leaves its gradients None, the kernels' path zeros
+            want = ({k: torch.zeros_like(v) if v.grad is None else v.grad.clone() for k, v in agent.named_parameters()},
+                    h0.grad.clone(), h_last.detach())
+        else:
+            for k, v in agent.named_parameters():
+                torch.testing.assert_close(v.grad, want[0][k], rtol=1e-4, atol=1e-5)
+            torch.testing.assert_close(h0.grad, want[1], rtol=1e-4, atol=1e-5)
+            torch.testing.assert_close(h_last.detach(), want[2], rtol=1e-5, atol=2e-5)
+
+
+@pytest.mark.parametrize("cls,use_rnn", [(RNNFusedAgent, False), (RNNAgent, True), (RNNAgent, False)])
+def test_unsupported_cases_return_the_loop(cls, use_rnn):
+    torch.manual_seed(2)
+    B, T1, n, K, m = 2, 3, 5, 20, 7
+    agent = cls(K, SimpleNamespace(hidden_dim=64, use_rnn=use_rnn, m=m)).to(DEV)
+    x = torch.randn((B, T1, n, K), device=DEV)
+    h0 = torch.randn((B * n, 64), device=DEV)
+    q, h = agent.unroll(x, h0)
+    q_loop, h_loop = _loop(agent, x, h0)
+    assert torch.equal(q, q_loop) and torch.equal(h, h_loop) and q.requires_grad

@@ -1,0 +1,131 @@
+"""SAPQLearner.train on a REDA-shaped problem (n = m = 64, L = 3, T = 20, 32 episodes sampled
+from a runner-filled ReplayBuffer, double_q), timed two ways in the same process, alternating:
+
+  fused    the agent's unroll() is asg_rnn_agent_unroll / asg_rnn_agent_unroll_backward
+  unfused  unroll() is forced to the per-step loop (args.unfused_unroll): the live network the
+           PyTorch module under autograd, the target network one asg_rnn_agent_forward per
+           step -- what a learner had before the unroll kernels
+
+Device events around each train() call after warm-up; one JSON line: median ms per train
+step of both paths, their spread (max - min over the repeats), the ratio, and the forward /
+backward kernel times alone.  `faster` is true when the fused median beats the unfused one
+by more than the unfused path's own spread.
+
+    python tools/bench_learner.py [--repeats 10] [--warmup 3] [--episodes 32]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+
+
+def timed(fn, repeats):
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--repeats", type=int, default=10)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--episodes", type=int, default=32)
+    p.add_argument("--n", type=int, default=64)
+    p.add_argument("--T", type=int, default=20)
+    o = p.parse_args()
+    if o.repeats < 5:
+        p.error("--repeats must be at least 5")
+    from marl_sap_amd import _lib
+    from marl_sap_amd.components import ReplayBuffer
+    from marl_sap_amd.controllers import REGISTRY as mac_REGISTRY
+    from marl_sap_amd.learners import REGISTRY as le_REGISTRY
+    from marl_sap_amd.modules.agents import rnn_agent
+    from marl_sap_amd.runners import REGISTRY as r_REGISTRY
+
+    dev = torch.device("cuda", 0)
+    E, n, T = o.episodes, o.n, o.T
+    a = bench.parse(["--n", str(n), "--m", str(n), "--T", str(T), "--cpu-baseline", "0", "--secondary", "0"])
+    args = bench.make_args(
+        a, E, selector="sap", agent="rnn", use_rnn=True, reuse_batch=False, epsilon_start=0.1, epsilon_finish=0.1,
+        mixer=None, lr=5e-4, gamma=0.99, grad_norm_clip=10.0, double_q=True, target_update_interval_or_tau=0.01,
+        standardise_rewards=True, standardise_returns=False, learner_log_interval=10 ** 12,
+        use_mps_action_selection=False, unfused_unroll=False)
+    runner = r_REGISTRY["gpu"](args, bench.NullLogger())
+    env = runner.get_env()
+    torch.manual_seed(a.seed)
+    mac = mac_REGISTRY["basic_mac"](env.scheme, {"agents": n}, args)
+    mac.to(dev)
+    runner.setup(env.scheme, {"agents": n}, env.preprocess, mac)
+    learner = le_REGISTRY["sap_q_learner"](mac, env.scheme, bench.NullLogger(), args)
+    buf = ReplayBuffer(env.scheme, {"agents": n}, E, T + 1, preprocess=env.preprocess, device=dev)
+    buf.insert_episode_batch(runner.run(test_mode=False))
+    batch = buf.sample(E, rng=np.random.RandomState(a.seed))
+    agents = (mac.agent, learner.target_mac.agent)
+
+    step = [0]
+
+    def train(unfused):
+        for ag in agents:
+            ag.args.unfused_unroll = unfused
+        learner.train(batch, step[0], step[0])
+        step[0] += 1
+
+    for _ in range(o.warmup):
+        train(False)
+        train(True)
+    fused, unfused = [], []
+    for _ in range(o.repeats):  # alternating, so drift hits both alike
+        fused += timed(lambda: train(False), 1)
+        unfused += timed(lambda: train(True), 1)
+    for ag in agents:
+        ag.args.unfused_unroll = False
+
+    # the two kernels alone, on the batch's inputs
+    x = mac._build_sequence_inputs(batch).detach()
+    ag = mac.agent
+    ps = [t.detach() for t in (ag.fc1.weight, ag.fc1.bias, ag.rnn.weight_ih, ag.rnn.weight_hh, ag.rnn.bias_ih,
+                               ag.rnn.bias_hh, ag.fc2.weight, ag.fc2.bias)]
+    B, T1, _, K = x.shape
+    R = B * n
+    q, h_all, save = rnn_agent._unroll_launch(x, None, *ps, True)
+    fwd = timed(lambda: rnn_agent._unroll_launch(x, None, *ps, True), o.repeats)
+    dh_q = torch.randn((T1 * R, 64), device=dev)
+    dgi = torch.empty((T1 * R, 192), device=dev)
+    dghn, dx1 = torch.empty((T1 * R, 64), device=dev), torch.empty((T1 * R, 64), device=dev)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def bwd_kernel():
+        _lib.check(_lib.lib().asg_rnn_agent_unroll_backward(
+            vp(dh_q), None, vp(save), vp(h_all), None, 0, vp(ps[2]), vp(ps[3]), T1, R, 64, ag.n_out, 1, vp(dgi),
+            vp(dghn), vp(dx1), None, _lib.stream_ptr(dev)))
+
+    bwd_kernel()
+    bwd = timed(bwd_kernel, o.repeats)
+
+    med = statistics.median
+    f, u = med(fused), med(unfused)
+    f_spread, u_spread = max(fused) - min(fused), max(unfused) - min(unfused)
+    print(json.dumps({
+        "metric": "sap_q_learner_train_ms", "shape": {"episodes": E, "n": n, "m": n, "L": a.L, "T": T, "K": K},
+        "repeats": o.repeats, "fused_ms": round(f, 4), "unfused_ms": round(u, 4),
+        "fused_spread_ms": round(f_spread, 4), "unfused_spread_ms": round(u_spread, 4),
+        "ratio_unfused_over_fused": round(u / f, 3), "faster": bool(u - f > u_spread),
+        "fwd_kernel_ms": round(med(fwd), 4), "bwd_kernel_ms": round(med(bwd), 4)}))
+
+
+if __name__ == "__main__":
+    main()
