@@ -292,14 +292,14 @@ int asg_epsilon_greedy(const float *q, const int64_t q_strides[3], const uint8_t
  * contiguous.  Outputs h_out [R][hidden], q_out [R][n_out], contiguous.  hidden must be 64,
  * 1 <= n_out <= 512 (the real envs' m, e.g. 450; a partial last 16-task tile is masked). */
 int64_t asg_rnn_agent_packed_size(int K, int hidden, int n_out, int use_rnn);
-/* Which layers of this build run their f32 products as three-way-split bf16 MFMAs (six cross
- * products, fp32-level accuracy; asg_agent.hip): bit 0 = GRU (default), bit 1 = fc1.  The
- * rest run f32 MFMAs.  For roofline accounting (bench.py); results match either way. */
+/* The MFMA mode of the fallback kernel (256 < n_out <= 512, asg_agent.hip): always 1 = the
+ * GRU's f32 products as three-way-split bf16 MFMAs (six cross products, fp32-level accuracy),
+ * the other layers on f32 MFMAs.  For roofline accounting (bench.py). */
 int asg_rnn_agent_mfma_mode(void);
-/* The MFMA mode of the kernel asg_rnn_agent_forward / _select run for this shape (16-B
- * aligned rows): 4 = every layer's f32 products on two-way-split f16 MFMAs (the split-f16
- * kernel: GRU, K % 32 == 0, n_out % 16 == 0, 16 <= n_out <= 256; accuracy vs float64 at or
- * below PyTorch fp32's, tests/test_gpu_agent.py), else asg_rnn_agent_mfma_mode(). */
+/* The MFMA mode of the kernel asg_rnn_agent_forward / _select run for this shape: 4 = every
+ * layer's f32 products on two-way-split f16 MFMAs (the split-f16 kernel: any K >= 1 with
+ * 1 <= n_out <= 256, GRU or Linear; accuracy vs float64 at or below PyTorch fp32's,
+ * tests/test_gpu_agent.py), else asg_rnn_agent_mfma_mode(). */
 int asg_rnn_agent_mode(int K, int hidden, int n_out, int use_rnn);
 int asg_rnn_agent_pack(const float *W1, const float *W_ih, const float *W_hh, const float *W2, int K,
                        int hidden, int n_out, int use_rnn, void *packed, void *hip_stream);

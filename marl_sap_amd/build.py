@@ -31,7 +31,7 @@ def needs_build():
 
 
 def build(force=False, verbose=False, out=None, extra=()):
-    """Build the library (`out`/`extra`: experiment variants, e.g. -DASG_AGENT_WAVES=3 into
+    """Build the library (`out`/`extra`: experiment variants, e.g. -DASG_AGENT_ONEHOT=0 into
     build/, loaded with ASG_LIB_PATH; the product library is always LIB)."""
     if out is None and not force and not needs_build():
         return LIB

@@ -1,4 +1,6 @@
-// asg_agent.hip -- fused RNNAgent forward for action selection (gfx950, f32 MFMA).
+// asg_agent.hip -- the RNNAgent forward for 256 < n_out <= 512: f32 fc1 / fc2, split-bf16 GRU
+// (gfx950).  Every shape with n_out <= 256 runs the split-f16 path (asg_h2.hip); the entry
+// points here (pack, forward, forward + selection) hand those over and keep the rest.
 //
 // RNNAgent.forward (modules/agents/rnn_agent.py:23-31) over all B*n agent rows of one
 // env step, in ONE pass over the observation slab:
@@ -8,17 +10,18 @@
 //     h' = n + z * (h - n)
 //   or h' = relu(x @ W_rnn^T + b_rnn)                             (use_rnn = False)
 //     q  = h' @ W2^T + b2
-// The PyTorch path runs this as 4 hipBLASLt GEMMs plus the GRU cell's elementwise kernel
-// (which also writes a 5*hidden backward workspace per row): ~6 GB of HBM traffic per
-// step at 64 agents x 16,384 envs.  Here every intermediate stays in registers / LDS:
-// HBM sees the observation rows once, h in, h' and q out.
+// Every intermediate stays in registers / LDS: HBM sees the observation rows once, h in, h'
+// and q out.
 //
-// Arithmetic: v_mfma_f32_16x16x4_f32 -- exact fp32 products, fp32 accumulation (a k-ordered
-// fmaf chain), i.e. fp32 like the reference; only the summation order differs from
-// hipBLASLt's (and the r/z gates add the input and hidden products in one accumulator).
+// Arithmetic: fc1, the Linear layer and fc2 on v_mfma_f32_16x16x4_f32 -- exact fp32 products,
+// fp32 accumulation (a k-ordered fmaf chain); only the summation order differs from
+// hipBLASLt's.  The GRU's products on bf16 MFMAs with a three-way operand split (below).
 // One wave owns 32 agent rows; all activations stay in registers (see the transposed
-// formulation below), weights come from L1/L2 in a pre-packed fragment order.
-#include <cstring>
+// formulation below), W1 comes from L1/L2 in a pre-packed fragment order, the recurrent
+// weights (and W2 when it fits beside them) from LDS.
+//
+// Also here, for every agent path: stream_cus, onehot_prefix_enabled and the W1^T pack of
+// the one-hot prefix (launch_w1t_pack, used by the split-f16 pack).
 #include <type_traits>
 
 #include "asg_agent_common.h"
@@ -27,76 +30,29 @@
 // add/mul as numpy does.  The agent's results are fp32-accurate, not bit-matched to a
 // reference order, so its elementwise math (bias epilogues, GRU gates, Q unscaling) may
 // fuse into FMAs: fewer VALU instructions, one rounding instead of two.
-#ifndef ASG_AGENT_CONTRACT
-#define ASG_AGENT_CONTRACT 1
-#endif
-#if ASG_AGENT_CONTRACT
 #pragma clang fp contract(fast)
-#endif
 
 namespace asg {
 
-
-// row tiles of 16 per wave (ASG_AGENT_NT = 2: 32 rows per wave at 2 waves per SIMD;
-// 1: 16 rows per wave, fewer registers, more waves per SIMD)
-#ifndef ASG_AGENT_NT
-#define ASG_AGENT_NT 2
-#endif
-constexpr int kNT = ASG_AGENT_NT;
+constexpr int kNT = 2;  // 16-row tiles per wave: 32 rows per wave at 2 waves per SIMD
 constexpr int kRowsPerWave = 16 * kNT;
-#ifndef ASG_AGENT_WAVES
-#define ASG_AGENT_WAVES 2  // waves per SIMD the register budget is fitted to
-#endif
-
-// ASG_AGENT_STAMPS (profiling builds only): s_memtime at the phase boundaries of the
-// first tiles of workgroup 0's waves, read back with asg_debug_agent_stamps()
-#ifdef ASG_AGENT_STAMPS
-__device__ unsigned long long g_agent_stamps[16][4][8];  // [wave][tile][stamp]
-__device__ int g_agent_tile[16];
-#define ASG_STAMP(k)                                                                                     \
-    do {                                                                                                 \
-        if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {                                                \
-            const int w_ = threadIdx.x >> 6, t_ = g_agent_tile[w_];                                      \
-            if (t_ < 4) g_agent_stamps[w_][t_][k] = __builtin_amdgcn_s_memtime();                       \
-            if (k == 7) g_agent_tile[w_] = t_ + 1;                                                        \
-        }                                                                                                \
-    } while (0)
-#else
-#define ASG_STAMP(k) \
-    do {             \
-    } while (0)
-#endif
+constexpr int kLdsWavesPerSimd = 2;  // waves per SIMD the register budget is fitted to
+constexpr int kLdsWaves = 4 * kLdsWavesPerSimd;
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// GRU products on bf16 MFMAs with a three-way operand split (ASG_AGENT_GRU_X3, default on):
-// an f32 x is truncated into hi + mid + lo bf16 parts with x == hi + mid + lo exactly (each
-// residual is exact and fits 8 significant bits), and x . w is summed from the six cross
-// products down to 2^-16 relative (hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid): the
-// dropped terms are below 2^-22 relative, so the gates match the fp32 module to ~1e-7.
-// Each bf16 MFMA covers 32 k at 16 cycles, the f32 MFMA 4 k at 32 cycles: 6 bf16 vs 8 f32
-// MFMAs per 32-deep k-slice = 2.7x less matrix-pipe time.  Non-finite inputs come out NaN.
-#ifndef ASG_AGENT_GRU_X3
-#define ASG_AGENT_GRU_X3 1
-#endif
-// fc1 the same way (-DASG_AGENT_FC1_X3=1; needs K % 32 == 0): measured 0.714 vs 0.702 ms with
-// the f32 fc1 -- its W1 planes (96 KiB) do not fit next to the GRU planes in LDS, and one
-// output tile of L2 prefetch does not cover their latency -- so off by default
-#ifndef ASG_AGENT_FC1_X3
-#define ASG_AGENT_FC1_X3 0
-#endif
-// fc2 the same way (-DASG_AGENT_FC2_X3=1): W2's hi + mid planes take W2's 16 KiB of LDS
-// (n_out = 64), its lo plane is read through L2
-#ifndef ASG_AGENT_FC2_X3
-#define ASG_AGENT_FC2_X3 0
-#endif
+// GRU products on bf16 MFMAs with a three-way operand split: an f32 x is truncated into
+// hi + mid + lo bf16 parts with x == hi + mid + lo exactly (each residual is exact and fits 8
+// significant bits), and x . w is summed from the six cross products down to 2^-16 relative
+// (hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid): the dropped terms are below 2^-22 relative,
+// so the gates match the fp32 module to ~1e-7.  Each bf16 MFMA covers 32 k at 16 cycles, the
+// f32 MFMA 4 k at 32 cycles: 6 bf16 vs 8 f32 MFMAs per 32-deep k-slice = 2.7x less
+// matrix-pipe time.  Non-finite inputs come out NaN.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // packed W_ih / W_hh: [gate 3][slab hb 4][k-slice 2][plane 3][lane 64] x 8 bf16
 constexpr int kGruX3F4 = 3 * 4 * 2 * 3 * 64;
-// float4 count of one packed GRU matrix (W_ih or W_hh)
-constexpr int kGruF4 = ASG_AGENT_GRU_X3 ? kGruX3F4 : 4 * 12 * 64;
 __device__ __forceinline__ int gru_x3_idx(int g, int hb, int s, int plane, int lane) {
     return (((g * 4 + hb) * 2 + s) * 3 + plane) * 64 + lane;
 }
@@ -124,12 +80,6 @@ __device__ __forceinline__ void split3(const float (&x)[8], u32x4v &h, u32x4v &m
         l[p] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, sb), __builtin_bit_cast(uint32_t, sa), 0x07060302u);
     }
 }
-// element j of the split back to f32 (exact)
-__device__ __forceinline__ float join3(const u32x4v &h, const u32x4v &m, const u32x4v &l, int j) {
-    const int sh = (j & 1) ? 0 : 16;
-    auto part = [&](const u32x4v &v) { return __builtin_bit_cast(float, (v[j >> 1] << sh) & 0xffff0000u); };
-    return (part(h) + part(m)) + part(l);
-}
 // sum of the six significant cross products of (wh, wm, wl) . (xh, xm, xl)
 __device__ __forceinline__ f32x4 mfma_x3(const u32x4v (&w)[3], const u32x4v (&x)[3], f32x4 c) {
     c = mfma_bf16(w[0], x[0], c);
@@ -146,22 +96,16 @@ __device__ __forceinline__ float4 ldg4(const float *p, bool ok) {
 }
 
 // GRU nonlinearities on the hardware transcendental units (v_exp_f32, v_rcp_f32): a few
-// ulp from the correctly rounded libm forms, far inside the 1e-5 parity tolerance, and
-// about 5% of the kernel's time.  -DASG_AGENT_EXACT_MATH restores expf / tanhf.
-#ifndef ASG_AGENT_EXACT_MATH
+// ulp from the correctly rounded libm forms, far inside the 1e-5 parity tolerance.
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 2.0f * sigmoidf_(2.0f * x) - 1.0f; }
-#else
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { return tanhf(x); }
-#endif
 
 // Packed weight layout ("fragment order"): for W [C][K] row-major (torch nn.Linear), block
 // (t, ct) holds, for lane l, W[16 ct + (l & 15)][16 t + 4 (l >> 4) .. + 3] as one float4,
 // so one wave loads a whole MFMA B-operand chunk as 1 KiB of contiguous memory.  K is
-// zero-padded to a multiple of 16.  Offsets (in float4) of the four matrices:
-//   W1: [K16/16][4][64]; W_ih: [4][12][64]; W_hh: [4][12][64] (GRU) ; W2: [4][nq][64],
-//   nq = ceil(n_out / 16) (zero rows pad the last output tile)
+// zero-padded to a multiple of 16.  The packed buffer, in float4:
+//   W1: [K16/16][4][64]; GRU: W_ih, W_hh as bf16 planes (kGruX3F4 each), Linear: W_rnn
+//   [4][4][64]; W2: [4][nq][64], nq = ceil(n_out / 16) (zero rows pad the last output tile)
 __device__ __forceinline__ int64_t pk(int t, int ct, int nct, int lane) { return ((int64_t)t * nct + ct) * 64 + lane; }
 
 __global__ void pack_weights_kernel(const float *W, int C, int K, float4 *out) {
@@ -193,24 +137,20 @@ __global__ void pack_weights_kernel(const float *W, int C, int K, float4 *out) {
 // t = mt, so activations go from layer to layer in registers: no LDS, no transposes, no
 // barriers.  One wave owns 32 rows (nt = 0, 1); lane (r, q) = (l & 15, l >> 4).
 // ---------------------------------------------------------------------------------
-// GEN = false: the bench shapes (K % 32 == 0 with 16-B aligned rows, n_out % 16 == 0, n_out
-// <= 256).  GEN = true: any K, any n_out <= 512 (checked by the ABI): guarded scalar row
-// loads, and the last output tile partial when n_out % 16 != 0 (zero weight rows, masked
-// bias / Q / availability).  A lane keeps 4 availability bits per output tile in two u64
-// (tiles 0-15, 16-31; the second only with GEN).  The general path costs ~3 % at the
-// bench shape, hence the two instantiations.
+// Any K, any n_out <= 512 (checked by the ABI): guarded row loads, and the last output tile
+// partial when n_out % 16 != 0 (zero weight rows, masked bias / Q / availability).  A lane
+// keeps 4 availability bits per output tile in two u64 (tiles 0-15, 16-31).
 
 // (the fused epsilon-greedy epilogue, select_finish, is in asg_agent_common.h)
 
-template <bool RNN, bool SEL, bool GEN>
+// W2l: W2 staged in LDS (w2l_on), else W2p is read through L2
+template <bool RNN, bool SEL>
 __device__ __forceinline__ void agent_rows(
     int64_t row0, const float *__restrict__ X, int64_t xs, int64_t R, int K, const float *__restrict__ Hin, int64_t hs,
     const float4 *__restrict__ W1p, const float *__restrict__ b1, const float4 *__restrict__ Wihp,
     const float *__restrict__ bih, const float4 *__restrict__ Whhp, const float *__restrict__ bhh,
     const float4 *__restrict__ W2p, const float *__restrict__ b2, int nout, float *__restrict__ Hout,
-    float *__restrict__ Q, const SelectArgs &sel, const float *__restrict__ W1T, int P,
-    const u32x4v *__restrict__ W1x3, const u32x4v *W2hm = nullptr, const u32x4v *__restrict__ W2lo = nullptr,
-    const float4 *W2l = nullptr, bool w2l_on = false) {
+    float *__restrict__ Q, const SelectArgs &sel, const float4 *W2l, bool w2l_on) {
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     if (row0 >= R) return;  // whole wave idle
     int64_t rows[kNT];
@@ -221,7 +161,6 @@ __device__ __forceinline__ void agent_rows(
         ok[nt] = rows[nt] < R;
     }
 
-    ASG_STAMP(0);
     // ---- h_in fragments (B operand of W_hh, and h of the GRU update): issued before fc1 so
     // they arrive under its MFMAs (issued after it, every tile's GRU waited on them) -------
     float4 hB[4][kNT];
@@ -229,15 +168,7 @@ __device__ __forceinline__ void agent_rows(
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int nt = 0; nt < kNT; ++nt)
-            // rows past R read row 0 (their results are discarded): unconditional loads
-            // keep the memory counters countable (no exec-masked branches)
-            hB[t][nt] = GEN ? ldg4(Hin + (ok[nt] ? rows[nt] : 0) * hs + 16 * t + 4 * q, RNN && Hin && ok[nt])
-                            : ((RNN && Hin) ? *reinterpret_cast<const float4 *>(Hin + (ok[nt] ? rows[nt] : 0) * hs +
-                                                                               16 * t + 4 * q)
-                                            : make_float4(0.f, 0.f, 0.f, 0.f));
-#ifdef ASG_AGENT_H_EARLY
-    __builtin_amdgcn_sched_barrier(0);  // issue them here, not next to the GRU
-#endif
+            hB[t][nt] = ldg4(Hin + (ok[nt] ? rows[nt] : 0) * hs + 16 * t + 4 * q, RNN && Hin && ok[nt]);
 
     // ---- fc1: x^T = relu(W1 X^T + b1), X rows streamed from HBM, 2 chunks in flight ----
     f32x4 xB[4][kNT];
@@ -254,14 +185,11 @@ __device__ __forceinline__ void agent_rows(
         for (int nt = 0; nt < kNT; ++nt) xr[nt] = X + (ok[nt] ? rows[nt] : 0) * xs;
         const int nk = (K + 15) / 16;
         // float4 row loads when K, the row stride and X are 16-B aligned; else guarded scalars
-        const bool xvec = !GEN || (((K | xs) & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0);
+        const bool xvec = ((K | xs) & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
         float4 aA[kNT], wA[4], aB[kNT], wB[4];
         auto load = [&](int t, float4 (&a4)[kNT], float4 (&w4)[4]) {
             const int k = 16 * t + 4 * q;
-            if (!GEN) {  // K % 32 == 0, aligned rows: every chunk is in bounds
-#pragma unroll
-                for (int nt = 0; nt < kNT; ++nt) a4[nt] = *reinterpret_cast<const float4 *>(xr[nt] + k);
-            } else if (xvec) {
+            if (xvec) {
 #pragma unroll
                 for (int nt = 0; nt < kNT; ++nt) a4[nt] = ldg4(xr[nt] + k, ok[nt] && k < K);
             } else {
@@ -286,153 +214,21 @@ __device__ __forceinline__ void agent_rows(
                     for (int nt = 0; nt < kNT; ++nt)
                         acc[mt][nt] = mfma4(comp(w4[mt], e), comp(a4[nt], e), acc[mt][nt]);
         };
-        // ping-pong over two register buffers, unrolled by two: a buffer is refilled right
-        // after its chunk's MFMAs, so two chunks stay in flight without register copies
-        // (a rotating a0 = a1 form compiles to copies that wait for the newest loads)
-        // one-hot prefix (onehot_prefix): when every row of the tile holds at most one
-        // nonzero in its first P inputs and that entry is exactly 1 (the mock env's
-        // onehot(previous task), or zeros at t = 0), those P / 16 chunks contribute
-        // W1[:, a] -- added from W1^T -- and their MFMAs are skipped; any other input
-        // (checked per tile) runs the full MFMA loop.
-        int t0 = 0;
-        if (!GEN && P > 0) {
-            int pos[kNT];
-            bool bad = false;
+        // two register buffers: a buffer is refilled right after its chunk's MFMAs are issued,
+        // so two chunks stay in flight
+        load(0, aA, wA);
+        if (nk > 1) load(1, aB, wB);
+        for (int t = 0; t < nk; ++t) {
+            float4 a4[kNT];
 #pragma unroll
-            for (int nt = 0; nt < kNT; ++nt) pos[nt] = -1;
-            for (int t4 = 0; t4 < P / 16; t4 += 4) {  // P % 64 == 0 or P / 16 < 4: guarded
-                float4 pa[4][kNT];
+            for (int i = 0; i < kNT; ++i) a4[i] = aA[i];
+            float4 w4[4] = {wA[0], wA[1], wA[2], wA[3]};
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
+            for (int i = 0; i < kNT; ++i) aA[i] = aB[i];
 #pragma unroll
-                    for (int nt = 0; nt < kNT; ++nt)
-                        pa[c][nt] = (t4 + c < P / 16)
-                                        ? *reinterpret_cast<const float4 *>(xr[nt] + 16 * (t4 + c) + 4 * q)
-                                        : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int nt = 0; nt < kNT; ++nt)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float v = comp(pa[c][nt], e);
-                            const bool one = v == 1.0f;
-                            bad |= (one && pos[nt] >= 0) || (!one && v != 0.0f);
-                            pos[nt] = one ? 16 * (t4 + c) + 4 * q + e : pos[nt];
-                        }
-            }
-            bool rows_ok = true;  // a row's 1 may sit in only one of its 4 lanes
-#pragma unroll
-            for (int nt = 0; nt < kNT; ++nt) {
-                const uint64_t mk = __ballot(pos[nt] >= 0);
-                const uint64_t g0 = mk & 0xffffull, g1 = (mk >> 16) & 0xffffull, g2 = (mk >> 32) & 0xffffull,
-                               g3 = mk >> 48;
-                rows_ok = rows_ok && ((g0 & g1) | (g0 & g2) | (g0 & g3) | (g1 & g2) | (g1 & g3) | (g2 & g3)) == 0;
-            }
-            if (rows_ok && __ballot(bad) == 0) {
-                t0 = P / 16;
-#pragma unroll
-                for (int nt = 0; nt < kNT; ++nt) {
-                    int a = pos[nt];
-                    a = max(a, __shfl_xor(a, 16));
-                    a = max(a, __shfl_xor(a, 32));
-                    if (a >= 0) {
-#pragma unroll
-                        for (int mt = 0; mt < 4; ++mt) {
-                            const float4 w = *reinterpret_cast<const float4 *>(W1T + a * kHid + 16 * mt + 4 * q);
-                            acc[mt][nt] += f32x4{w.x, w.y, w.z, w.w};
-                        }
-                    }
-                }
-            }
-        }
-#ifdef ASG_AGENT_FC1_PINGPONG
-        if (!GEN && ((nk - t0) & 1) == 0) {
-            // nk even (K % 32 == 0): ping-pong over two register buffers, each refilled right
-            // after its chunk's MFMAs, with scheduling barriers so the refills are not sunk
-            // next to their uses.  Measured slower (0.894 vs 0.868 ms): obs latency is not
-            // what bounds this kernel (tools/agent_ab.py, ASG_AB_L2X).
-            load(t0, aA, wA);
-            __builtin_amdgcn_sched_barrier(0);
-            load(t0 + 1, aB, wB);
-            __builtin_amdgcn_sched_barrier(0);
-            const int last = nk - 1;
-            for (int t = t0; t < nk; t += 2) {
-                chunk(aA, wA);
-                __builtin_amdgcn_sched_barrier(0);
-                load(t + 2 < last ? t + 2 : last, aA, wA);
-                __builtin_amdgcn_sched_barrier(0);
-                chunk(aB, wB);
-                __builtin_amdgcn_sched_barrier(0);
-                load(t + 3 < last ? t + 3 : last, aB, wB);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else
-#endif
-        {
-#if ASG_AGENT_FC1_X3
-            if (!GEN && W1x3 && (t0 & 1) == 0) {
-                // fc1 on bf16 MFMAs, three-way split (see split3): k-slice sl = f32 chunks
-                // 2 sl and 2 sl + 1 of the row, whose float4s are exactly the gru_x3_k order;
-                // W1 planes from L2 one output tile ahead, X one slice ahead
-                const int ns = nk >> 1;
-                auto load_x = [&](int sl, float4 (&xb)[2][kNT]) {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < kNT; ++nt)
-                            xb[c][nt] = *reinterpret_cast<const float4 *>(xr[nt] + 32 * sl + 16 * c + 4 * q);
-                };
-                auto load_w = [&](int sl, int mt, u32x4v (&w)[3]) {
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) w[pl] = W1x3[((sl * 4 + mt) * 3 + pl) * 64 + lane];
-                };
-                float4 xa[2][kNT], xn[2][kNT];
-                u32x4v wc[3], wn[3];
-                load_x(t0 >> 1, xa);
-                if ((t0 >> 1) + 1 < ns) load_x((t0 >> 1) + 1, xn);
-                load_w(t0 >> 1, 0, wc);
-                for (int sl = t0 >> 1; sl < ns; ++sl) {
-                    u32x4v a3[kNT][3];
-#pragma unroll
-                    for (int nt = 0; nt < kNT; ++nt) {
-                        const float v8[8] = {xa[0][nt].x, xa[0][nt].y, xa[0][nt].z, xa[0][nt].w,
-                                             xa[1][nt].x, xa[1][nt].y, xa[1][nt].z, xa[1][nt].w};
-                        split3(v8, a3[nt][0], a3[nt][1], a3[nt][2]);
-                    }
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < kNT; ++nt) xa[c][nt] = xn[c][nt];
-                    if (sl + 2 < ns) load_x(sl + 2, xn);
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) {
-                        if (mt < 3) load_w(sl, mt + 1, wn);
-                        else if (sl + 1 < ns) load_w(sl + 1, 0, wn);
-#pragma unroll
-                        for (int nt = 0; nt < kNT; ++nt) acc[mt][nt] = mfma_x3(wc, a3[nt], acc[mt][nt]);
-#pragma unroll
-                        for (int pl = 0; pl < 3; ++pl) wc[pl] = wn[pl];
-                    }
-                }
-            } else
-#endif
-            {
-            load(t0, aA, wA);
-            if (nk > t0 + 1) load(t0 + 1, aB, wB);
-            for (int t = t0; t < nk; ++t) {
-                float4 a4[kNT];
-#pragma unroll
-                for (int i = 0; i < kNT; ++i) a4[i] = aA[i];
-                float4 w4[4] = {wA[0], wA[1], wA[2], wA[3]};
-#pragma unroll
-                for (int i = 0; i < kNT; ++i) aA[i] = aB[i];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wA[i] = wB[i];
-                if (t + 2 < nk) load(t + 2, aB, wB);
-                chunk(a4, w4);
-            }
-            }
+            for (int i = 0; i < 4; ++i) wA[i] = wB[i];
+            if (t + 2 < nk) load(t + 2, aB, wB);
+            chunk(a4, w4);
         }
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
@@ -442,7 +238,6 @@ __device__ __forceinline__ void agent_rows(
                 for (int v = 0; v < 4; ++v) xB[mt][nt][v] = fmaxf(acc[mt][nt][v], 0.f);
     }
 
-    ASG_STAMP(1);
     // ---- recurrent layer -> h'^T in registers (hp[hb] = B operand of fc2's chunk hb) ----
     bool h_zero = false;
     if (RNN) {
@@ -457,7 +252,6 @@ __device__ __forceinline__ void agent_rows(
     f32x4 hp[4][kNT];
 #pragma unroll
     for (int hb = 0; hb < 4; ++hb) {
-        if (hb > 0) ASG_STAMP(3 + hb);
         if (RNN) {
             // gate pre-activations: r and z sum the input and hidden products in one
             // accumulator; n keeps them apart (n = tanh(i_n + r * h_n))
@@ -481,7 +275,6 @@ __device__ __forceinline__ void agent_rows(
             }
             // a tile whose h is all zero (BasicMAC.init_hidden at t = 0) skips the W_hh
             // products (exact zeros): a third of the GRU's MFMAs on those steps
-#if ASG_AGENT_GRU_X3
             const u32x4v *Wih3 = reinterpret_cast<const u32x4v *>(Wihp);
             const u32x4v *Whh3 = reinterpret_cast<const u32x4v *>(Whhp);
             auto gates = [&](auto with_h) {
@@ -520,32 +313,6 @@ __device__ __forceinline__ void agent_rows(
                     }
                 }
             };
-#else
-            auto gates = [&](auto with_h) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    float4 wc[6];
-#pragma unroll
-                    for (int g = 0; g < 3; ++g) {
-                        wc[g] = Wihp[pk(t, 4 * g + hb, 12, lane)];
-                        if (with_h) wc[3 + g] = Whhp[pk(t, 4 * g + hb, 12, lane)];
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int nt = 0; nt < kNT; ++nt) {
-                            gr[nt] = mfma4(comp(wc[0], e), xB[t][nt][e], gr[nt]);
-                            gz[nt] = mfma4(comp(wc[1], e), xB[t][nt][e], gz[nt]);
-                            gni[nt] = mfma4(comp(wc[2], e), xB[t][nt][e], gni[nt]);
-                            if (with_h) {
-                                gr[nt] = mfma4(comp(wc[3], e), comp(hB[t][nt], e), gr[nt]);
-                                gz[nt] = mfma4(comp(wc[4], e), comp(hB[t][nt], e), gz[nt]);
-                                gnh[nt] = mfma4(comp(wc[5], e), comp(hB[t][nt], e), gnh[nt]);
-                            }
-                        }
-                }
-            };
-#endif
             if (h_zero)
                 gates(std::false_type{});
             else
@@ -586,7 +353,6 @@ __device__ __forceinline__ void agent_rows(
                     make_float4(hp[hb][nt][0], hp[hb][nt][1], hp[hb][nt][2], hp[hb][nt][3]);
     }
 
-    ASG_STAMP(2);
     // ---- selection state: (env, agent) of each row, running argmax, availability bits ----
     const uint8_t *arow[kNT];
     bool av4 = false;
@@ -621,9 +387,9 @@ __device__ __forceinline__ void agent_rows(
 
     // ---- fc2 one 16-output tile at a time: q^T = W2 h'^T + b2; Q store and/or argmax ----
     const int nct = (nout + 15) / 16;
-    const bool qvec = !GEN || (nout & 3) == 0;
+    const bool qvec = (nout & 3) == 0;
     for (int c = 0; c < nct; ++c) {
-        const bool full = !GEN || 16 * c + 16 <= nout;  // wave-uniform: only the last tile can be partial
+        const bool full = 16 * c + 16 <= nout;  // wave-uniform: only the last tile can be partial
         const int j0 = 16 * c + 4 * q;          // this lane's first task of the tile
         uint32_t av[kNT];  // 4 availability bits of this lane's tasks, per row
 #pragma unroll
@@ -659,26 +425,6 @@ __device__ __forceinline__ void agent_rows(
         f32x4 a2[kNT];
 #pragma unroll
         for (int nt = 0; nt < kNT; ++nt) a2[nt] = f32x4{bq.x, bq.y, bq.z, bq.w};
-#if ASG_AGENT_FC2_X3
-        if (!GEN && W2lo) {
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-                u32x4v a3[kNT][3];
-#pragma unroll
-                for (int nt = 0; nt < kNT; ++nt) {
-                    const float v8[8] = {hp[2 * sl][nt][0],     hp[2 * sl][nt][1],     hp[2 * sl][nt][2],
-                                         hp[2 * sl][nt][3],     hp[2 * sl + 1][nt][0], hp[2 * sl + 1][nt][1],
-                                         hp[2 * sl + 1][nt][2], hp[2 * sl + 1][nt][3]};
-                    split3(v8, a3[nt][0], a3[nt][1], a3[nt][2]);
-                }
-                const u32x4v w3[3] = {W2hm[((c * 2 + sl) * 2 + 0) * 64 + lane], W2hm[((c * 2 + sl) * 2 + 1) * 64 + lane],
-                                      W2lo[(c * 2 + sl) * 64 + lane]};
-#pragma unroll
-                for (int nt = 0; nt < kNT; ++nt) a2[nt] = mfma_x3(w3, a3[nt], a2[nt]);
-            }
-        } else
-#endif
-        {
         float4 w2[4];
         if (w2l_on) {  // staged in LDS: ds_read, not a flat load through a merged pointer
             typedef const f32x4 __attribute__((address_space(3))) * lds_f4p;
@@ -698,7 +444,6 @@ __device__ __forceinline__ void agent_rows(
             for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int nt = 0; nt < kNT; ++nt) a2[nt] = mfma4(comp(w2[t], e), hp[t][nt][e], a2[nt]);
-        }
 #pragma unroll
         for (int nt = 0; nt < kNT; ++nt) {
             if (Q && ok[nt]) {
@@ -721,108 +466,52 @@ __device__ __forceinline__ void agent_rows(
                     bj[nt] = b ? j : bj[nt];
                 }
                 const uint64_t bits = (uint64_t)av[nt] << (4 * (c & 15));
-                if (!GEN || c < 16) amask[nt][0] |= bits;
+                if (c < 16) amask[nt][0] |= bits;
                 else amask[nt][1] |= bits;
             }
         }
     }
-    ASG_STAMP(3);
-    if (!SEL) {
-        ASG_STAMP(7);
-        return;
-    }
-
-    select_finish<GEN>(best, bj, amask, rows, ok, oidx, nct, sel, q);
-    ASG_STAMP(7);
+    if (!SEL) return;
+    select_finish<true>(best, bj, amask, rows, ok, oidx, nct, sel, q);
 }
 
-// One wave per 32 rows, weights read through L1/L2 (any n_out).
-template <bool RNN, bool SEL, bool GEN>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ASG_AGENT_WAVES))) rnn_agent_fwd_kernel(
-    const float *__restrict__ X, int64_t xs, int64_t R, int K, const float *__restrict__ Hin, int64_t hs,
-    const float4 *__restrict__ W1p, const float *__restrict__ b1, const float4 *__restrict__ Wihp,
-    const float *__restrict__ bih, const float4 *__restrict__ Whhp, const float *__restrict__ bhh,
-    const float4 *__restrict__ W2p, const float *__restrict__ b2, int nout, float *__restrict__ Hout,
-    float *__restrict__ Q, SelectArgs sel, const float *__restrict__ W1T, int P, const u32x4v *__restrict__ W1x3) {
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * kRowsPerWave;
-    agent_rows<RNN, SEL, GEN>(row0, X, xs, R, K, Hin, hs, W1p, b1, Wihp, bih, Whhp, bhh, W2p, b2, nout, Hout, Q, sel,
-                              W1T, P, W1x3);
-}
-
-// Persistent variant: one 512-thread workgroup per CU copies the recurrent and output
-// weights (packed fragments) into LDS once, then its 8 waves walk 256-row tiles; the
-// gate and fc2 A operands become conflict-free ds_read_b128 instead of L2 round trips.
-#ifndef ASG_AGENT_LDS_WAVES_PER_SIMD
-#define ASG_AGENT_LDS_WAVES_PER_SIMD 2
-#endif
-constexpr int kLdsWaves = 4 * ASG_AGENT_LDS_WAVES_PER_SIMD;
-// ASG_AGENT_NUM_VGPR: cap of the persistent kernel's unified (arch + acc) VGPRs, e.g. 224
-// (amdgpu_num_vgpr counts half the unified file on gfx950) to leave room for a co-resident
-// env-step wave on the same SIMD; default: the compiler's choice under 2 waves/SIMD.
-#ifdef ASG_AGENT_NUM_VGPR
-#define ASG_AGENT_VGPR_ATTR __attribute__((amdgpu_num_vgpr(ASG_AGENT_NUM_VGPR / 2)))
-#else
-#define ASG_AGENT_VGPR_ATTR
-#endif
-template <bool RNN, bool SEL, bool GEN>
-__global__ void __launch_bounds__(64 * kLdsWaves) __attribute__((amdgpu_waves_per_eu(ASG_AGENT_LDS_WAVES_PER_SIMD)))
-ASG_AGENT_VGPR_ATTR
+// Persistent: one 512-thread workgroup per CU copies the recurrent weights (and the output
+// weights when they fit: nrf4 float4 of packed fragments from Wrp) into LDS once, then its 8
+// waves walk 256-row tiles; the gate and fc2 A operands become conflict-free ds_read_b128
+// instead of L2 round trips.
+template <bool RNN, bool SEL>
+__global__ void __launch_bounds__(64 * kLdsWaves) __attribute__((amdgpu_waves_per_eu(kLdsWavesPerSimd)))
 rnn_agent_lds_kernel(
     const float *__restrict__ X, int64_t xs, int64_t R, int K, const float *__restrict__ Hin, int64_t hs,
     const float4 *__restrict__ W1p, const float *__restrict__ b1, const float4 *__restrict__ Wrp, int64_t nrf4,
     const float *__restrict__ bih, const float *__restrict__ bhh, const float *__restrict__ b2, int nout,
-    float *__restrict__ Hout, float *__restrict__ Q, SelectArgs sel, const float *__restrict__ W1Tg, int P,
-    int64_t wr_f4, int64_t w2_lds, int64_t w1t_lds, const u32x4v *__restrict__ W1x3,
-    const u32x4v *__restrict__ W2hmg, const u32x4v *__restrict__ W2lo, int64_t w2hm_f4) {
+    float *__restrict__ Hout, float *__restrict__ Q, int64_t wr_f4, int64_t w2_lds, SelectArgs sel) {
     extern __shared__ float4 s_w[];
-    // W2's split hi + mid planes (w2hm_f4 > 0) are staged where the f32 W2 would sit
-    const int64_t lead = w2hm_f4 > 0 ? wr_f4 : nrf4;
-    for (int64_t i = threadIdx.x; i < lead; i += blockDim.x) s_w[i] = Wrp[i];
-    for (int64_t i = threadIdx.x; i < w2hm_f4; i += blockDim.x)
-        s_w[wr_f4 + i] = reinterpret_cast<const float4 *>(W2hmg)[i];
+    for (int64_t i = threadIdx.x; i < nrf4; i += blockDim.x) s_w[i] = Wrp[i];
     __syncthreads();
-    // always an LDS address (a select with NULL would make it a flat pointer); used only when
-    // w2hm_f4 > 0, signalled to agent_rows through W2lo != NULL
-    const u32x4v *W2hm = reinterpret_cast<const u32x4v *>(s_w + wr_f4);
     const float4 *Wih = s_w;
-    const float4 *Whh = s_w + (RNN ? kGruF4 : 0);
+    const float4 *Whh = s_w + (RNN ? kGruX3F4 : 0);
     // W2 staged after the recurrent weights when it fit (w2_lds >= 0), else read through L2
     const float4 *W2 = Wrp + wr_f4;
     const float4 *W2l = s_w + (w2_lds >= 0 ? w2_lds : 0);
-    // W1^T of the one-hot prefix: read through L2 (a select between an LDS and a global
-    // pointer would make every gather a flat load); w1t_lds is unused
-    (void)w1t_lds;
-    const float *W1T = W1Tg;
     const int64_t ntiles = (R + kLdsWaves * kRowsPerWave - 1) / (kLdsWaves * kRowsPerWave);
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = (tile * kLdsWaves + (threadIdx.x >> 6)) * kRowsPerWave;
-        agent_rows<RNN, SEL, GEN>(row0, X, xs, R, K, Hin, hs, W1p, b1, Wih, bih, Whh, bhh, W2, b2, nout, Hout, Q, sel,
-                                  W1T, P, W1x3, W2hm, W2lo, W2l, w2_lds >= 0 && !W2lo);
+        agent_rows<RNN, SEL>(row0, X, xs, R, K, Hin, hs, W1p, b1, Wih, bih, Whh, bhh, W2, b2, nout, Hout, Q, sel, W2l,
+                             w2_lds >= 0);
     }
 }
 
-// One-hot input prefix of the f32 / split-bf16 kernels: the first P = n_out inputs may be a
-// one-hot block (the mock env's obs starts with onehot(previous task),
-// mock_constellation_env.py:141-152).  The pack adds W1^T of those P columns ([P][64], one
-// float4 per 4 hidden units), and a wave tile whose prefix rows are verified one-hot (or
-// zero) adds W1[:, a] instead of running the prefix chunks' MFMAs.  P = 0 (no section) unless
-// n_out % 16 == 0 and n_out < K.
-static int onehot_prefix(int K, int nout) { return (nout % 16 == 0 && nout < K && K % 32 == 0) ? nout : 0; }
-// W2 as three bf16 planes for the split fc2: hi + mid planes [c][sl 2][plane 2][lane 64],
-// then the lo planes [c][sl 2][lane 64] (x 8 bf16)
-static int64_t w2x3_f4(int nout) { return ASG_AGENT_FC2_X3 ? (int64_t)((nout + 15) / 16) * 2 * 3 * 64 : 0; }
-// W1 as three bf16 planes for the split fc1 ([K / 32][mt 4][plane 3][lane 64] x 8 bf16)
-static int64_t w1x3_f4(int K) { return ASG_AGENT_FC1_X3 && K % 32 == 0 ? (int64_t)(K / 32) * 4 * 3 * 64 : 0; }
+// float4 counts of the packed sections: W1, the recurrent layer, W2
+static int64_t w1_f4(int K) { return (int64_t)((K + 15) / 16) * 4 * 64; }
+static int64_t wr_f4(int use_rnn) { return use_rnn ? 2 * kGruX3F4 : 4 * 4 * 64; }
+static int64_t w2_f4(int nout) { return 4 * (int64_t)((nout + 15) / 16) * 64; }
 
 // float4 count of the packed weight buffer: the split-f16 layout (asg_h2.hip) for every shape
-// it takes, else the f32 / split-bf16 layout below
+// it takes, else the f32 / split-bf16 layout above
 int64_t rnn_agent_packed_f4(int K, int nout, int use_rnn) {
     if (h2_ok(K, nout)) return h2_packed_f4(K, nout, use_rnn);
-    const int64_t w1 = (int64_t)((K + 15) / 16) * 4 * 64;
-    const int64_t wr = use_rnn ? 2 * kGruF4 : 4 * 4 * 64;
-    const int64_t w2 = 4 * (int64_t)((nout + 15) / 16) * 64;
-    const int64_t w1t = (int64_t)onehot_prefix(K, nout) * 16;
-    return w1 + wr + w2 + w1t + w1x3_f4(K) + w2x3_f4(nout);
+    return w1_f4(K) + wr_f4(use_rnn) + w2_f4(nout);
 }
 
 // W_ih / W_hh [3 * 64][64] -> kGruX3F4 x 8 bf16 (gru_x3_idx order, k order gru_x3_k)
@@ -840,35 +529,7 @@ __global__ void pack_gru_x3_kernel(const float *W, u32x4v *out) {
     out[i] = pl == 0 ? h : (pl == 1 ? m : l);
 }
 
-__global__ void pack_w1_x3_kernel(const float *W1, int K, u32x4v *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (K / 32) * 4 * 3 * 64) return;
-    const int lane = i & 63, pl = (i >> 6) % 3, mt = (i / (64 * 3)) & 3, sl = i / (64 * 3 * 4);
-    const int row = 16 * mt + (lane & 15), q = lane >> 4;
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = W1[(int64_t)row * K + gru_x3_k(sl, q, j)];
-    u32x4v h, m, l;
-    split3(x, h, m, l);
-    out[i] = pl == 0 ? h : (pl == 1 ? m : l);
-}
-
-__global__ void pack_w2_x3_kernel(const float *W2, int nout, u32x4v *out) {
-    const int nct = (nout + 15) / 16;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // over [c][sl][lane]
-    if (i >= nct * 2 * 64) return;
-    const int lane = i & 63, sl = (i >> 6) & 1, c = i >> 7;
-    const int row = 16 * c + (lane & 15), q = lane >> 4;
-    float x[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = row < nout ? W2[(int64_t)row * kHid + gru_x3_k(sl, q, j)] : 0.f;
-    u32x4v h, m, l;
-    split3(x, h, m, l);
-    out[((c * 2 + sl) * 2 + 0) * 64 + lane] = h;
-    out[((c * 2 + sl) * 2 + 1) * 64 + lane] = m;
-    out[nct * 2 * 2 * 64 + (c * 2 + sl) * 64 + lane] = l;
-}
-
+// W1^T of the first P columns ([P][64] f32): the one-hot prefix section of the split-f16 pack
 __global__ void pack_w1t_kernel(const float *W1, int K, int P, float *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;  // out[a][u] = W1[u][a]
     if (i < P * kHid) out[i] = W1[(int64_t)(i % kHid) * K + i / kHid];
@@ -890,30 +551,15 @@ hipError_t launch_rnn_agent_pack(const float *W1, const float *Wih, const float 
     };
     one(W1, kHid, K);
     if (use_rnn) {
-#if ASG_AGENT_GRU_X3
         for (const float *W : {Wih, Whh}) {
             hipLaunchKernelGGL(pack_gru_x3_kernel, dim3((kGruX3F4 + 255) / 256), dim3(256), 0, s, W,
                                reinterpret_cast<u32x4v *>(p));
             p += kGruX3F4;
         }
-#else
-        one(Wih, 3 * kHid, kHid);
-        one(Whh, 3 * kHid, kHid);
-#endif
     } else {
         one(Wih, kHid, kHid);
     }
     one(W2, nout, kHid);
-    const int P = onehot_prefix(K, nout);
-    (void)launch_w1t_pack(W1, K, P, reinterpret_cast<float *>(p), s);
-    p += (int64_t)P * 16;
-    if (const int64_t n3 = w1x3_f4(K))
-        hipLaunchKernelGGL(pack_w1_x3_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, W1, K,
-                           reinterpret_cast<u32x4v *>(p));
-    p += w1x3_f4(K);
-    if (w2x3_f4(nout))
-        hipLaunchKernelGGL(pack_w2_x3_kernel, dim3((unsigned)(((nout + 15) / 16 * 128 + 255) / 256)), dim3(256), 0, s,
-                           W2, nout, reinterpret_cast<u32x4v *>(p));
     return hipGetLastError();
 }
 
@@ -937,18 +583,13 @@ int stream_cus(hipStream_t s) {
     return last_n < ncu ? last_n : ncu;
 }
 
-// Build-time A/B switches (no runtime environment knobs in the shipped library):
-// -DASG_AGENT_ONEHOT=0 disables the one-hot prefix shortcut (and with it the episode kernel,
-// whose tiles rely on it); -DASG_AGENT_LDS_WEIGHTS=0 selects the L2-weight kernel.
+// Build-time A/B switch (no runtime environment knobs in the shipped library):
+// -DASG_AGENT_ONEHOT=0 disables the split-f16 path's one-hot prefix shortcut (and with it the
+// rollout kernel, whose tiles rely on it).
 #ifndef ASG_AGENT_ONEHOT
 #define ASG_AGENT_ONEHOT 1
 #endif
-#ifndef ASG_AGENT_LDS_WEIGHTS
-#define ASG_AGENT_LDS_WEIGHTS 1
-#endif
 bool onehot_prefix_enabled() { return ASG_AGENT_ONEHOT != 0; }
-
-static bool use_lds_weights() { return ASG_AGENT_LDS_WEIGHTS != 0; }
 
 hipError_t launch_rnn_agent_fwd(const float *X, int64_t xs, int64_t R, int K, const float *Hin, int64_t hs,
                                 const float4 *packed, const float *b1, const float *bih, const float *bhh,
@@ -956,69 +597,31 @@ hipError_t launch_rnn_agent_fwd(const float *X, int64_t xs, int64_t R, int K, co
                                 hipStream_t s) {
     if (h2_ok(K, nout)) return launch_h2_agent(X, xs, R, K, Hin, hs, packed, b1, bih, bhh, b2, nout, use_rnn, Hout, Q,
                                                sel, s);
-    const int64_t rows_per_block = 4 * kRowsPerWave;
-    const int64_t blocks = (R + rows_per_block - 1) / rows_per_block;
     const float4 *W1p = packed;
-    const float4 *Wihp = W1p + (int64_t)((K + 15) / 16) * 4 * 64;
-    const int64_t wr_f4 = use_rnn ? 2 * kGruF4 : 4 * 4 * 64;
-    const int64_t w2_f4 = 4 * (int64_t)((nout + 15) / 16) * 64;
-    const float4 *Whhp = Wihp + (use_rnn ? kGruF4 : 4 * 4 * 64);
-    const float4 *W2p = Wihp + wr_f4;
+    const float4 *Wrp = W1p + w1_f4(K);
     const SelectArgs sa = sel ? *sel : SelectArgs{};
-    const int P = onehot_prefix_enabled() ? onehot_prefix(K, nout) : 0;
-    // recurrent weights in LDS, then the output weights when they fit (n_out <= 64 with the
-    // GRU), then the one-hot prefix's W1^T when it fits too (else each is read through L2)
+    // LDS image: the recurrent weights (GRU: 144 KiB, Linear: 16 KiB), then the output weights
+    // when they fit beside them (else read through L2)
     constexpr size_t kLdsMax = 160 * 1024;
-    int64_t nrf4 = wr_f4, w2_lds = -1, w1t_lds = -1;
-    const float *W1Tg = reinterpret_cast<const float *>(W2p + w2_f4);
-    const u32x4v *W1x3 = w1x3_f4(K) ? reinterpret_cast<const u32x4v *>(W2p + w2_f4 + (int64_t)onehot_prefix(K, nout) * 16)
-                                    : nullptr;
-    if ((size_t)(nrf4 + w2_f4) * sizeof(float4) <= kLdsMax) {
+    const int64_t wr = wr_f4(use_rnn);
+    int64_t nrf4 = wr, w2_lds = -1;
+    if ((size_t)(nrf4 + w2_f4(nout)) * sizeof(float4) <= kLdsMax) {
         w2_lds = nrf4;
-        nrf4 += w2_f4;
+        nrf4 += w2_f4(nout);
     }
-    // split fc2 (ASG_AGENT_FC2_X3): hi + mid planes in W2's LDS slot, lo through L2
-    const int64_t w2hm_f4 = w2x3_f4(nout) ? (int64_t)((nout + 15) / 16) * 2 * 2 * 64 : 0;
-    const u32x4v *W2x3g = w2x3_f4(nout) ? reinterpret_cast<const u32x4v *>(
-                                             W2p + w2_f4 + (int64_t)onehot_prefix(K, nout) * 16 + w1x3_f4(K))
-                                       : nullptr;
     const size_t lds = (size_t)nrf4 * sizeof(float4);
-    const bool gen = (K & 31) != 0 || (xs & 3) != 0 || (reinterpret_cast<uintptr_t>(X) & 15) != 0 || nout % 16 != 0 ||
-                     nout > 256;
-    // (the general-shape instantiation keeps the f32 W2 in that LDS slot)
-    const bool fc2x3 = use_rnn && !gen && W2x3g && w2_lds == wr_f4 && w2hm_f4 <= w2_f4;
-    if (use_lds_weights() && lds <= 160 * 1024) {
-        const int ncu = stream_cus(s);
-        const int64_t ntiles = (R + kLdsWaves * kRowsPerWave - 1) / (kLdsWaves * kRowsPerWave);
-        const unsigned grid = (unsigned)(ntiles < ncu ? ntiles : ncu);
-#define LL_(RNN, SEL, GEN)                                                                                   \
-    hipLaunchKernelGGL((rnn_agent_lds_kernel<RNN, SEL, GEN>), dim3(grid), dim3(64 * kLdsWaves), lds, s, X, xs, R, K, \
-                       Hin, hs, W1p, b1, Wihp, nrf4, bih, bhh, b2, nout, Hout, Q, sa, W1Tg, P, wr_f4, w2_lds, \
-                       w1t_lds, W1x3, fc2x3 ? W2x3g : nullptr, fc2x3 ? W2x3g + w2hm_f4 : nullptr, \
-                       fc2x3 ? w2hm_f4 : (int64_t)0)
-#define LG_(RNN, SEL) \
-    if (gen) LL_(RNN, SEL, true); else LL_(RNN, SEL, false)
-        if (use_rnn) {
-            if (sel) { LG_(true, true); } else { LG_(true, false); }
-        } else {
-            if (sel) { LG_(false, true); } else { LG_(false, false); }
-        }
-#undef LG_
-#undef LL_
-        return hipGetLastError();
-    }
-#define L_(RNN, SEL, GEN)                                                                                    \
-    hipLaunchKernelGGL((rnn_agent_fwd_kernel<RNN, SEL, GEN>), dim3(blocks), dim3(256), 0, s, X, xs, R, K, Hin, hs, \
-                       W1p, b1, Wihp, bih, Whhp, bhh, W2p, b2, nout, Hout, Q, sa, W1Tg, P, W1x3)
-#define LG_(RNN, SEL) \
-    if (gen) L_(RNN, SEL, true); else L_(RNN, SEL, false)
+    const int ncu = stream_cus(s);
+    const int64_t ntiles = (R + kLdsWaves * kRowsPerWave - 1) / (kLdsWaves * kRowsPerWave);
+    const unsigned grid = (unsigned)(ntiles < ncu ? ntiles : ncu);
+#define LL_(RNN, SEL)                                                                                              \
+    hipLaunchKernelGGL((rnn_agent_lds_kernel<RNN, SEL>), dim3(grid), dim3(64 * kLdsWaves), lds, s, X, xs, R, K, Hin, hs, \
+                       W1p, b1, Wrp, nrf4, bih, bhh, b2, nout, Hout, Q, wr, w2_lds, sa)
     if (use_rnn) {
-        if (sel) { LG_(true, true); } else { LG_(true, false); }
+        if (sel) LL_(true, true); else LL_(true, false);
     } else {
-        if (sel) { LG_(false, true); } else { LG_(false, false); }
+        if (sel) LL_(false, true); else LL_(false, false);
     }
-#undef LG_
-#undef L_
+#undef LL_
     return hipGetLastError();
 }
 
@@ -1035,20 +638,11 @@ hipError_t launch_rnn_agent_select(const float *X, int64_t xs, int64_t R, int K,
 
 }  // namespace asg
 
-extern "C" int asg_rnn_agent_mfma_mode(void) { return (ASG_AGENT_GRU_X3 ? 1 : 0) | (ASG_AGENT_FC1_X3 ? 2 : 0); }
+// 1: the GRU's products on split-bf16 MFMAs (the only form of the fallback kernel)
+extern "C" int asg_rnn_agent_mfma_mode(void) { return 1; }
 extern "C" int asg_rnn_agent_mode(int K, int hidden, int n_out, int use_rnn) {
     (void)use_rnn;
     if (hidden != 64) return -1;
     if (asg::h2_ok(K, n_out)) return 4;  // split-f16 (asg_h2.hip), GRU or Linear
     return asg_rnn_agent_mfma_mode();
 }
-
-#ifdef ASG_AGENT_STAMPS
-// profiling builds: copy the stamps out (uint64 [16][4][8]) and re-arm
-extern "C" int asg_debug_agent_stamps(unsigned long long *out) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(asg::g_agent_stamps), sizeof(asg::g_agent_stamps)) != hipSuccess) return -2;
-    static const int zero[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(asg::g_agent_tile), zero, sizeof(zero)) != hipSuccess) return -2;
-    return 0;
-}
-#endif

@@ -16,8 +16,6 @@
 #include "asg_internal.h"
 #include "lsa_wave.h"
 
-#include <mutex>
-
 namespace asg {
 
 // ------------------------------------------------------------------------------------
@@ -1050,71 +1048,21 @@ hipError_t launch_reset(const asg_batch_view &bv, const EnvState &st, int ts, bo
 
 // The MT19937 mode's reset without its row write: the draws (and the float32 table) only --
 // the episode launch that follows writes the reset row (asg_reset_rollout in the same-seed mode)
-// The draws (one wave per env, latency-bound: the sequential MT19937 consumption) and the table
-// writer (float64 bump evaluations, compute-bound) are pipelined over env chunks on two streams:
-// chunk c's table kernel runs on an auxiliary stream beside chunk c + 1's draws (disjoint envs),
-// each table chunk after its own draws (an event) and after everything before the reset on the
-// caller's stream (so the previous episode's table readers are done), the caller's stream waiting
-// for the last table chunk.  One auxiliary stream and event set per device (handles of one device
-// used from several host threads at once would share them).
-#ifndef ASG_RESET_CHUNKS
-#define ASG_RESET_CHUNKS 1  // 2 / 4 / 8 measured no faster (r6 A/B): one launch each
-#endif
-namespace {
-struct ResetAux {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[ASG_RESET_CHUNKS + 1] = {};
-};
-hipError_t reset_aux(ResetAux **out) {
-    static std::mutex mu;
-    static ResetAux aux[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lk(mu);
-    ResetAux &a = aux[dev];
-    if (!a.s) {
-        if ((e = hipStreamCreateWithFlags(&a.s, hipStreamNonBlocking)) != hipSuccess) return e;
-        for (auto &ev : a.ev)
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-    }
-    *out = &a;
-    return hipSuccess;
-}
-}  // namespace
-
+// Two launches on the caller's stream: the draws (one wave per env, latency-bound: the
+// sequential MT19937 consumption), then the table writer (float64 bump evaluations,
+// compute-bound).  Both kernels take the launch's first env (0: every env in one launch;
+// pipelining env chunks over two streams measured no faster).
 hipError_t launch_reset_draws(const EnvState &st, bool construct, hipStream_t s) {
     if (st.rng_mode != ASG_RNG_MT19937) return hipErrorInvalidValue;
     const size_t lds = sizeof(uint32_t) * (ASG_MT_TEMPER_ON_READ ? 2 : 4) * kMtN + sizeof(int) * st.m;
     const bool gen = st.benefit_mode != ASG_BENEFIT_INJECTED;
     const int R = mt_table_rows(st.m);
-    const int K = (gen && st.E >= 1024) ? ASG_RESET_CHUNKS : 1;
-    if (K == 1) {
-        hipLaunchKernelGGL(mt_reset_kernel, dim3(st.E), dim3(64), lds, s, st.mt, st, st.mtpar, construct && gen, gen,
-                           (int64_t)0);
-        hipError_t err = hipGetLastError();
-        if (err != hipSuccess || !gen) return err;
-        hipLaunchKernelGGL(mt_table_kernel, dim3(st.E), dim3(256), mt_table_lds(R, st.m), s, st.mtpar, st, R,
-                           (int64_t)0);
-        return hipGetLastError();
-    }
-    ResetAux *ax = nullptr;
-    hipError_t err = reset_aux(&ax);
-    if (err != hipSuccess) return err;
-    for (int c = 0; c < K; ++c) {
-        const int64_t e0 = st.E * c / K, e1 = st.E * (c + 1) / K;
-        hipLaunchKernelGGL(mt_reset_kernel, dim3((unsigned)(e1 - e0)), dim3(64), lds, s, st.mt, st, st.mtpar,
-                           construct, true, e0);
-        if ((err = hipGetLastError()) != hipSuccess) return err;
-        if ((err = hipEventRecord(ax->ev[c], s)) != hipSuccess) return err;
-        if ((err = hipStreamWaitEvent(ax->s, ax->ev[c], 0)) != hipSuccess) return err;
-        hipLaunchKernelGGL(mt_table_kernel, dim3((unsigned)(e1 - e0)), dim3(256), mt_table_lds(R, st.m), ax->s,
-                           st.mtpar, st, R, e0);
-        if ((err = hipGetLastError()) != hipSuccess) return err;
-    }
-    if ((err = hipEventRecord(ax->ev[K], ax->s)) != hipSuccess) return err;
-    return hipStreamWaitEvent(s, ax->ev[K], 0);
+    hipLaunchKernelGGL(mt_reset_kernel, dim3(st.E), dim3(64), lds, s, st.mt, st, st.mtpar, construct && gen, gen,
+                       (int64_t)0);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess || !gen) return err;
+    hipLaunchKernelGGL(mt_table_kernel, dim3(st.E), dim3(256), mt_table_lds(R, st.m), s, st.mtpar, st, R, (int64_t)0);
+    return hipGetLastError();
 }
 
 hipError_t launch_step(const asg_batch_view &bv, const EnvState &st, int ts, int k, hipStream_t s, bool assign_ready) {

@@ -2,125 +2,19 @@
 // rollout kernel that runs the mock env's transitions, the agent and the epsilon-greedy
 // selection for a range of steps of every env -- a whole episode in one launch.
 //
-// Reference: modules/agents/rnn_agent.py:23-31 (fc1 -> ReLU -> GRUCell | Linear + ReLU ->
-// fc2), controllers/basic_controller.py:19-48 (select_actions), action_selectors/
-// classic_selectors.py:28-54 (epsilon-greedy), envs/mock_constellation_env.py:94-175 (reset,
-// step, pre-transition data), runners/episode_runner.py:60-127 (the loop this kernel fuses:
-// select(0); for t: step(t), select(t + 1)).
-//
-// Split-f16 products.  Every f32 operand x (pre-scaled by a power of two so |x| < 2^15) is
-// split x ~ h + l with h = RNE_f16(x), l = RNE_f16(x - h) (x - h is exact in f32):
-// |x - h - l| <= 2^-22 |x|, and a product is summed as wh.xh + wh.xl + wl.xh on
-// v_mfma_f32_16x16x32_f16 (the dropped wl.xl is below 2^-22 relative): 3 MFMAs per 32-deep
-// slice, products exact in the f32 accumulator, summation in f32 -- fp32-level accuracy
-// (tests/test_gpu_agent.py measures it against float64).
-//
-// Transposed layers: out^T = W . act^T.  The MFMA A operand is a packed weight fragment (1 KiB
-// per wave, contiguous), the B operand an activation fragment; with the 16x16 layouts the
-// accumulator of output tile mt IS the B operand of the next layer's k-chunk, so fc1 ->
-// recurrent layer -> fc2 hand activations over in registers.  One wave owns 32 agent rows
-// (two 16-row tiles nt); lane (r, q) = (l & 15, l >> 4) holds rows r and 16 + r.
-//
-// Scales are per ROW (each lane's accumulator column is one row): weights by 2^sw per
-// matrix (pack time), a row's activations by 2^s from the row's own max |x| (a reduction
-// over its 4 lanes).  So every row's result is a function of that row's inputs alone -- the
-// same whichever rows share its wave tile (envs of 20 agents in 32-row tiles, sharded runs,
-// the fused rollout's one-env tiles vs the agent kernel's flat tiles: bit-identical).  fc1's
-// input scale is chosen before the values are seen (2^11: |x| < 16 needs no retry) and a
-// tile re-runs fc1 when some row would exceed 2^15 (that row at its own smaller scale).
-//
-// Geometry.  The input row is NB blocks of P values; each block is zero-padded to
-// Pp = roundup(P, 32) so a 32-deep slice never straddles two blocks.  For the mock env's
-// obs ([onehot(previous task) | B(k) .. B(k + L - 1)], P = m, NB = L + 1) block 0 is the
-// one-hot prefix: a tile whose block 0 is verified one-hot (or zero) adds W1[:, a] (one
-// gathered column per row) instead of running those slices' MFMAs.  Any other input is one
-// block (P = K).
-#include <type_traits>
-
-#include "asg_agent_common.h"
+// This file holds the host side of both (input geometry, weight packing, LDS plan, launch)
+// and the kernels instantiated here: the agent kernel, the pack kernels and the rollout
+// kernel's Philox epsilon-greedy instances.  The device code lives in two headers: h2_tile.h
+// (the split-f16 arithmetic and one wave tile of the agent) and rollout_tile.h (the rollout
+// tile and kernel, shared with asg_rollout_tab.hip and asg_rollout_q.hip, which hold the
+// other instances).
+#include "rollout_tile.h"
 
 #pragma clang fp contract(fast)
 
 namespace asg {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-typedef long long i64x2v __attribute__((ext_vector_type(2)));
-typedef const u32x4v __attribute__((address_space(3))) * lds_u4p;
-typedef const f32x4 __attribute__((address_space(3))) * lds_f4v;
-
-__device__ __forceinline__ f32x4 mfma_h(const u32x4v &a, const u32x4v &b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
-                                                  0);
-}
-// (wh, wl) . (xh, xl) = wh.xh + wh.xl + wl.xh; the correction terms first
-__device__ __forceinline__ f32x4 mfma_h2(const u32x4v (&w)[2], const u32x4v (&x)[2], f32x4 c) {
-    c = mfma_h(w[1], x[0], c);
-    c = mfma_h(w[0], x[1], c);
-    c = mfma_h(w[0], x[0], c);
-    return c;
-}
-// 8 (scaled) f32 -> f16 planes h, l (element j in half j & 1 of dword j >> 1)
-__device__ __forceinline__ void split2(const float (&x)[8], u32x4v &h, u32x4v &l) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const f16x2v hh = {(_Float16)x[2 * p], (_Float16)x[2 * p + 1]};
-        const float ra = x[2 * p] - (float)hh[0], rb = x[2 * p + 1] - (float)hh[1];
-        const f16x2v ll = {(_Float16)ra, (_Float16)rb};
-        h[p] = __builtin_bit_cast(uint32_t, hh);
-        l[p] = __builtin_bit_cast(uint32_t, ll);
-    }
-}
-// The split of 8 UNSCALED values at scale sc (a power of two): h = RNE_f16(x * sc) and the
-// residual fma(x, sc, -h) (exact in f32) rounded once to f16 by v_fma_mix{lo,hi}_f16.
-__device__ __forceinline__ void split2s(const float (&x)[8], float sc, u32x4v &h, u32x4v &l) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const f16x2v hh = {(_Float16)(x[2 * p] * sc), (_Float16)(x[2 * p + 1] * sc)};
-        const uint32_t hv = __builtin_bit_cast(uint32_t, hh);
-        uint32_t lv = 0;
-        asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "+v"(lv) : "v"(x[2 * p]), "v"(sc), "v"(hv));
-        asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-            : "+v"(lv)
-            : "v"(x[2 * p + 1]), "v"(sc), "v"(hv));
-        h[p] = hv;
-        l[p] = lv;
-    }
-}
-// max(m, |a|, |b|) in one v_max3_f32
-__device__ __forceinline__ float max3_abs(float m, float a, float b) {
-    float r;
-    asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float absmax4(float m, const float4 &v) { return max3_abs(max3_abs(m, v.x, v.y), v.z, v.w); }
-__device__ __forceinline__ float absmax4(float m, const f32x4 &v) {
-    return max3_abs(max3_abs(m, v[0], v[1]), v[2], v[3]);
-}
-// 2^s as a float (s clamped to the normal range [-126, 127])
-__device__ __forceinline__ float pow2f(int s) {
-    s = s < -126 ? -126 : (s > 127 ? 127 : s);
-    return __builtin_bit_cast(float, (uint32_t)(s + 127) << 23);
-}
-// the scale exponent s with m * 2^s < 2^15 (m = max |x| >= 0), clamped to [lo, hi]
-__device__ __forceinline__ int h2_scale(float m, int lo, int hi) {
-    const int e = m > 0.f ? (int)((__builtin_bit_cast(uint32_t, m) >> 23) & 0xff) - 126 : -200;  // m < 2^e
-    const int s = 15 - e;
-    return s < lo ? lo : (s > hi ? hi : s);
-}
-// maximum over the 4 lanes of a row (q = 0..3: lanes l, l ^ 16, l ^ 32, l ^ 48); v >= 0
-__device__ __forceinline__ float row_max4(float v) {
-    const SwapPair a = swap16(__builtin_bit_cast(uint32_t, v));
-    const float x = fmaxf(__builtin_bit_cast(float, a.a), __builtin_bit_cast(float, a.b));
-    const SwapPair b = swap32(__builtin_bit_cast(uint32_t, x));
-    return fmaxf(__builtin_bit_cast(float, b.a), __builtin_bit_cast(float, b.b));
-}
-// element j of lane quad q of a 32-deep slice: units 4q + v of its two 16-tiles (the
-// accumulator layout of the layer before, so activations feed the MFMA in place)
-__host__ __device__ inline int slice_k(int q, int j) { return j < 4 ? 4 * q + j : 16 + 4 * q + j - 4; }
-
 // ---- geometry and packed layout -----------------------------------------------------------
-#if !ASG_H2_TU
 H2Geom h2_geom(int K, int nout) {
     H2Geom g;
     g.K = K;
@@ -135,702 +29,11 @@ H2Geom h2_geom(int K, int nout) {
     return g;
 }
 bool h2_ok(int K, int nout) { return K >= 1 && nout >= 1 && nout <= 256; }
-#endif
-
-// packed h2 section (u32x4v units): [header: int sw1, sw_r1, sw_r2, sw2]
-//   [W1 planes: slice Kp / 32][mt 4][plane 2][lane 64]
-//   [recurrent planes: GRU W_ih (gate 3)(hb 4)(slice 2)(plane 2)(lane 64), then W_hh; or the
-//    Linear W_rnn as one gate]
-//   [W2 planes: tile nct][slice 2][plane 2][lane 64]
-// preceded (one-hot prefix geometry) by W1^T of block 0: [P][64] f32
-constexpr int kGateF4 = 4 * 2 * 2 * 64;
-__host__ __device__ inline int64_t rec_f4(bool rnn) { return rnn ? 6 * kGateF4 : kGateF4; }
-__host__ __device__ inline int64_t w1s_f4(int Kp) { return (int64_t)(Kp / 32) * 4 * 2 * 64; }
-__host__ __device__ inline int64_t w2s_f4(int nct) { return (int64_t)nct * 2 * 2 * 64; }
-__device__ __forceinline__ int gate_idx(int g, int hb, int sl, int pl, int lane) {
-    return (((g * 4 + hb) * 2 + sl) * 2 + pl) * 64 + lane;
-}
-__device__ __forceinline__ int64_t w1_idx(int sl, int mt, int pl, int lane) {
-    return (((int64_t)sl * 4 + mt) * 2 + pl) * 64 + lane;
-}
-__device__ __forceinline__ int w2_idx(int c, int sl, int pl, int lane) { return ((c * 2 + sl) * 2 + pl) * 64 + lane; }
-static inline int64_t w1t_f4(const H2Geom &g) { return g.prefix ? (int64_t)g.P * 16 : 0; }
-#if !ASG_H2_TU
 int64_t h2_packed_f4(int K, int nout, int use_rnn) {
     const H2Geom g = h2_geom(K, nout);
     return w1t_f4(g) + 1 + w1s_f4(g.Kp) + rec_f4(use_rnn != 0) + w2s_f4(g.nct);
 }
-#endif
 
-// LDS image (u32x4v units): [recurrent planes][biases][W2 planes (W2L)][W1 slices][scratch]
-// biases (floats): b1 [64] | GRU: b_ir + b_hr, b_iz + b_hz, b_in, b_hn [4 x 64]; Linear: b_rnn,
-// 0, 0, 0 | b2 [16 nct] (zero past n_out)
-__host__ __device__ inline int64_t bias_f4(int nct) { return 80 + 4 * (int64_t)nct; }
-__host__ __device__ inline int64_t lds_w2_off(bool rnn, int nct) { return rec_f4(rnn) + bias_f4(nct); }
-__host__ __device__ inline int64_t lds_w1_off(bool rnn, int nct, bool w2l) {
-    return lds_w2_off(rnn, nct) + (w2l ? w2s_f4(nct) : 0);
-}
-
-struct H2Args {
-    const float *X;
-    int64_t xs, R;
-    H2Geom g;
-    int pre;           // one-hot gather shortcut on block 0 (prefix geometry, ASG_AGENT_ONEHOT)
-    const float *Hin;
-    int64_t hs;
-    const u32x4v *pk;  // h2 section
-    const float *W1T;  // [P][64] f32: W1 columns of block 0
-    const float *b1, *bi, *bh, *b2;  // GRU: b_ih, b_hh; Linear: b_rnn, unused
-    float *Hout, *Q;
-    SelectArgs sel;
-    int w1_lds;        // W1 slices [s0 + w1_off, s0 + w1_off + w1_lds) staged in LDS (s0 = pre ? Pp / 32 : 0)
-    int w1_off;        // 1: the first main slice (s0) stays in L2 (the rollout reads it before its stores)
-};
-
-constexpr int kH2NT = 2;                        // 16-row tiles per wave: 32 rows
-constexpr int kH2WavesPerSimd = 2;              // register budget 256 VGPRs
-constexpr int kH2Waves = 4 * kH2WavesPerSimd;   // waves per workgroup (one workgroup per CU)
-constexpr int kH2XBuf = 2;                      // observation slices in flight per wave in fc1
-constexpr int kH2SxInit = 11;                   // fc1 input scale of the first attempt
-// Timing-only switches (WRONG results; refused without -DASG_TIMING_EXPERIMENTS):
-// ASG_ROLLOUT_XSKIP bit 1: no batch row stores in the rollout tiles; bit 2: no one-hot W1
-// column gather (zeros); bit 4: fc1 slices that live in L2 read LDS slot 0 instead; bit 8:
-// h_t not loaded (constants); bit 16: h' not stored; bit 32: the tile's row stores go to a
-// small region that stays in L2 (env e & 7, batch row 1): same instructions, no HBM writes;
-// bit 64: the tiles' bump parameters from a cheap hash instead of Philox (VALU); bit 256: no env
-// transition between the steps (rewards, returns, the transition's rows); bit 512: the return
-// not summed in agent order (one readlane); bit 1024: the transition's rewards without the bump
-// (Philox + float64 exp: beta = 0); bit 2048: the compact table's quads not loaded (a constant,
-// the mask / expansion kept); bit 4096: the compact quads loaded but not expanded
-#if defined(ASG_ROLLOUT_XSKIP) && !defined(ASG_TIMING_EXPERIMENTS)
-#error "ASG_ROLLOUT_XSKIP gives wrong results: timing experiments only (-DASG_TIMING_EXPERIMENTS)"
-#endif
-#ifndef ASG_ROLLOUT_XSKIP
-#define ASG_ROLLOUT_XSKIP 0
-#endif
-
-template <class A>
-__device__ __forceinline__ int h2_s0(A &a) { return a.pre ? (a.g.Pp >> 5) : 0; }
-
-template <bool RNN, bool W2L>
-__device__ __forceinline__ void h2_stage(const H2Args &a, u32x4v *s, int (&sw)[4]) {
-    const H2Geom &g = a.g;
-    const u32x4v *rec = a.pk + 1 + w1s_f4(g.Kp);  // recurrent planes, then W2
-    const int64_t nrec = rec_f4(RNN);
-    for (int64_t i = threadIdx.x; i < nrec; i += blockDim.x) s[i] = rec[i];
-    float *bs = reinterpret_cast<float *>(s + nrec);
-    for (int i = threadIdx.x; i < 5 * kHid + 16 * g.nct; i += blockDim.x) {
-        const int blk = i >> 6, u = i & 63;
-        float v;
-        if (blk == 0) v = a.b1[u];
-        else if (blk < 5) {
-            if (RNN) v = blk == 1 ? a.bi[u] + a.bh[u]
-                       : blk == 2 ? a.bi[kHid + u] + a.bh[kHid + u]
-                       : blk == 3 ? a.bi[2 * kHid + u] : a.bh[2 * kHid + u];
-            else v = blk == 1 ? a.bi[u] : 0.f;
-        } else {
-            const int j = i - 5 * kHid;
-            v = j < g.nout ? a.b2[j] : 0.f;
-        }
-        bs[i] = v;
-    }
-    if (W2L) {
-        const int64_t n2 = w2s_f4(g.nct), off = lds_w2_off(RNN, g.nct);
-        for (int64_t i = threadIdx.x; i < n2; i += blockDim.x) s[off + i] = rec[nrec + i];
-    }
-    {
-        const u32x4v *w1 = a.pk + 1 + w1_idx(h2_s0(a) + a.w1_off, 0, 0, 0);
-        const int64_t n1 = (int64_t)a.w1_lds * 4 * 2 * 64, off = lds_w1_off(RNN, g.nct, W2L);
-        for (int64_t i = threadIdx.x; i < n1; i += blockDim.x) s[off + i] = w1[i];
-    }
-    const int4 hdr = *reinterpret_cast<const int4 *>(a.pk);
-    sw[0] = hdr.x;
-    sw[1] = hdr.y;
-    sw[2] = hdr.z;
-    sw[3] = hdr.w;
-}
-
-// The recurrent layer, fc2 and selection of one 32-row wave tile (shared by the agent kernel
-// and the rollout kernel): xB = relu(fc1) fragments, hB = h_in rows (GRU).
-// ALLAV: every task is available (the rollout wrote avail = 1 itself).  act_lds (rollout):
-// also receives each row's selected task (index lrow0 + row within the tile).
-// 1: the GRU's (1 - z) n + z h takes h back from its split-f16 planes (h_hi + h_lo, exact to
-// 2^-22) instead of keeping the f32 h live through the gate products
-// 1: the GRU layer is compiled once per h_zero case (no branch between its hidden blocks)
-#ifndef ASG_GRU_HOIST
-#define ASG_GRU_HOIST 1
-#endif
-#ifndef ASG_H2_H_FROM_PLANES
-#define ASG_H2_H_FROM_PLANES 0
-#endif
-
-struct NoTailHook {
-    __device__ void operator()() const {}
-};
-
-// after_rec: called once the recurrent layer has consumed hB and stored h' (the rollout
-// issues the next agent tile's h_t loads there)
-template <int NT, bool RNN, bool SEL, bool W2L, bool ALLAV, bool GEN, class Hook = NoTailHook, class A>
-__device__ __forceinline__ void h2_tail(A &a, const u32x4v *Wl, const int (&sw)[4], int64_t row0,
-                                        const int64_t (&rows)[NT], const bool (&ok)[NT], const float4 (&hB)[4][NT],
-                                        const f32x4 (&xB)[4][NT], uint16_t *act_lds = nullptr, int lrow0 = 0,
-                                        const Hook &after_rec = Hook{}) {
-    // lane-derived addresses are recomputed here, not hoisted out of the callers' step / env
-    // loops (there they would be live across every tile and spill; their reloads would wait
-    // behind the tile stores in the in-order vmcnt queue)
-    int lane_ = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane_));
-    const int lane = lane_, r = lane & 15, q = lane >> 4;
-    const int nout = a.g.nout, nct = a.g.nct;
-    const lds_u4p Wr = (lds_u4p)Wl;
-    const lds_f4v Bs = (lds_f4v)(Wl + rec_f4(RNN));  // biases
-    // availability words of fc2's first four output tiles: issued now, used after the
-    // recurrent layer
-    auto &sel = a.sel;
-    const uint8_t *arow[NT];
-    int64_t oidx[NT];
-    bool av4 = false;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        arow[nt] = nullptr;
-        oidx[nt] = 0;
-    }
-    if (SEL) {
-        const int64_t b0 = row0 / sel.n;
-        const int i0 = (int)(row0 - b0 * sel.n);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            int64_t b = b0;
-            int i = i0 + 16 * nt + r;
-            while (i >= sel.n) {
-                i -= sel.n;
-                ++b;
-            }
-            arow[nt] = ALLAV ? nullptr : sel.avail + (ok[nt] ? b * sel.a0 + (int64_t)i * sel.a1 : 0);
-            oidx[nt] = b * sel.o0 + (int64_t)i * sel.o1;
-        }
-        av4 = !ALLAV && !GEN && ((reinterpret_cast<uintptr_t>(sel.avail) | (uintptr_t)sel.a0 | (uintptr_t)sel.a1) & 3u) == 0;
-    }
-    // 4 availability bytes of tasks 16 c + 4 q .. + 3 (0 past n_out)
-    auto load_av = [&](int c, int nt) -> uint32_t {
-        const int j0 = 16 * c + 4 * q;
-        if (!SEL || !ok[nt]) return 0u;
-        if (ALLAV) {
-            if (!GEN) return 0x01010101u;
-            const int nv = nout - j0;
-            return nv >= 4 ? 0x01010101u : (nv <= 0 ? 0u : (0x01010101u & ((1u << (8 * nv)) - 1u)));
-        }
-        const uint8_t *ap = arow[nt] + j0;
-        if (av4) return *reinterpret_cast<const uint32_t *>(ap);
-        uint32_t w = 0;
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-            if (!GEN || j0 + v < nout) w |= (uint32_t)ap[v] << (8 * v);
-        return w;
-    };
-    uint32_t avw[4][NT];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) avw[c][nt] = c < nct ? load_av(c, nt) : 0u;
-
-    // ---- recurrent layer: per-row scales, operand planes ---------------------------------
-    float mx[NT], mh[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        mx[nt] = 0.f;
-        mh[nt] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            mx[nt] = absmax4(mx[nt], xB[t][nt]);
-            if (RNN) mh[nt] = absmax4(mh[nt], hB[t][nt]);
-        }
-        mx[nt] = row_max4(mx[nt]);
-        if (RNN) mh[nt] = row_max4(mh[nt]);
-    }
-    int Sg[NT];
-    bool hz_all = true;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const bool hz = !RNN || !(mh[nt] > 0.f);  // zero h rows (init_hidden): no W_hh products
-        hz_all = hz_all && hz;
-        int s = min(sw[1] + h2_scale(mx[nt], -90, 90), hz ? 1000 : sw[2] + h2_scale(mh[nt], -90, 90));
-        Sg[nt] = s > 100 ? 100 : (s < -100 ? -100 : s);
-    }
-    const bool h_zero = !RNN || __ballot(!hz_all) == 0;  // wave-uniform: skip the W_hh MFMAs
-    u32x4v xP[2][NT][2], hP[2][NT][2];
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            float v8[8], h8[8];
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    v8[4 * c + v] = xB[2 * sl + c][nt][v];
-                    h8[4 * c + v] = RNN ? comp(hB[2 * sl + c][nt], v) : 0.f;
-                }
-            split2s(v8, pow2f(Sg[nt] - sw[1]), xP[sl][nt][0], xP[sl][nt][1]);
-            if (RNN) split2s(h8, pow2f(Sg[nt] - sw[2]), hP[sl][nt][0], hP[sl][nt][1]);
-        }
-    f32x4 hp[4][NT];
-    if (RNN) {
-        // sigmoid(g 2^-S) = 1 / (1 + 2^(g c1)), tanh(y 2^-S) = 2 / (1 + 2^(y c2)) - 1
-        float c1[NT], c2[NT], hun[NT], scS[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            c1[nt] = -1.4426950408889634f * pow2f(-Sg[nt]);
-            c2[nt] = 2.0f * c1[nt];
-            hun[nt] = pow2f(sw[2] - Sg[nt]);  // unscale of the h planes
-            scS[nt] = pow2f(Sg[nt]);
-        }
-        const lds_u4p Wih = Wr, Whh = (lds_u4p)(Wl + 3 * kGateF4);
-        // the whole recurrent layer per h_zero case: no branch between the four hidden blocks,
-        // so the scheduler can overlap one block's gate math with the next block's MFMAs
-        auto gru = [&](auto hz_tag) {
-        constexpr bool HZ = decltype(hz_tag)::value;
-#pragma unroll
-        for (int hb = 0; hb < 4; ++hb) {
-            // r and z sum the input and hidden products in one accumulator, from b_i + b_h;
-            // n keeps them apart (n = tanh(i_n + r * h_n))
-            const f32x4 br = Bs[16 + 4 * hb + q], bz = Bs[32 + 4 * hb + q], bn = Bs[48 + 4 * hb + q],
-                        bhn = Bs[64 + 4 * hb + q];
-            f32x4 gr[NT], gz[NT], gni[NT], gnh[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                gr[nt] = br * scS[nt];
-                gz[nt] = bz * scS[nt];
-                gni[nt] = bn * scS[nt];
-                gnh[nt] = bhn * scS[nt];
-            }
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl)
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const u32x4v w[2] = {Wih[gate_idx(g, hb, sl, 0, lane)], Wih[gate_idx(g, hb, sl, 1, lane)]};
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        f32x4 &acc_ = g == 0 ? gr[nt] : (g == 1 ? gz[nt] : gni[nt]);
-                        acc_ = mfma_h2(w, xP[sl][nt], acc_);
-                    }
-                }
-            if (!HZ && !h_zero) {
-#pragma unroll
-                for (int sl = 0; sl < 2; ++sl)
-#pragma unroll
-                    for (int g = 0; g < 3; ++g) {
-                        const u32x4v w[2] = {Whh[gate_idx(g, hb, sl, 0, lane)], Whh[gate_idx(g, hb, sl, 1, lane)]};
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            f32x4 &acc_ = g == 0 ? gr[nt] : (g == 1 ? gz[nt] : gnh[nt]);
-                            acc_ = mfma_h2(w, hP[sl][nt], acc_);
-                        }
-                    }
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const float rg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gr[nt][v] * c1[nt]));
-                    const float zg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gz[nt][v] * c1[nt]));
-                    const float ng =
-                        2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((gni[nt][v] + rg * gnh[nt][v]) * c2[nt])) -
-                        1.0f;
-#if ASG_H2_H_FROM_PLANES
-                    // h from its planes (h_hi + h_lo = h 2^sh to 2^-22 relative)
-                    const int j = 4 * (hb & 1) + v;
-                    const uint32_t dh = hP[hb >> 1][nt][0][j >> 1], dl = hP[hb >> 1][nt][1][j >> 1];
-                    const f16x2v ph = __builtin_bit_cast(f16x2v, dh), pl = __builtin_bit_cast(f16x2v, dl);
-                    const float hv = ((float)ph[j & 1] + (float)pl[j & 1]) * hun[nt];
-#else
-                    const float hv = comp(hB[hb][nt], v);  // the exact h (the planes carry it to 2^-22)
-#endif
-                    hp[hb][nt][v] = ng + zg * (hv - ng);
-                }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                if (ok[nt] && !(ALLAV && (ASG_ROLLOUT_XSKIP & 16)))
-                    *reinterpret_cast<float4 *>(a.Hout + rows[nt] * kHid + 16 * hb + 4 * q) =
-                        make_float4(hp[hb][nt][0], hp[hb][nt][1], hp[hb][nt][2], hp[hb][nt][3]);
-        }
-        };
-#if ASG_GRU_HOIST
-        if (h_zero) gru(std::true_type{});
-        else gru(std::false_type{});
-#else
-        gru(std::false_type{});  // h_zero tested per block inside (the round-4 form)
-#endif
-    } else {
-        // Linear + ReLU (use_rnn = False): h' = relu(W_rnn x + b_rnn), one gate of planes
-        float scS[NT], un[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            scS[nt] = pow2f(Sg[nt]);
-            un[nt] = pow2f(-Sg[nt]);
-        }
-#pragma unroll
-        for (int hb = 0; hb < 4; ++hb) {
-            const f32x4 bb = Bs[16 + 4 * hb + q];
-            f32x4 acc[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[nt] = bb * scS[nt];
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-                const u32x4v w[2] = {Wr[gate_idx(0, hb, sl, 0, lane)], Wr[gate_idx(0, hb, sl, 1, lane)]};
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma_h2(w, xP[sl][nt], acc[nt]);
-            }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-#pragma unroll
-                for (int v = 0; v < 4; ++v) hp[hb][nt][v] = fmaxf(acc[nt][v] * un[nt], 0.f);
-                if (ok[nt])
-                    *reinterpret_cast<float4 *>(a.Hout + rows[nt] * kHid + 16 * hb + 4 * q) =
-                        make_float4(hp[hb][nt][0], hp[hb][nt][1], hp[hb][nt][2], hp[hb][nt][3]);
-            }
-        }
-    }
-
-    after_rec();
-    // ---- fc2 (+ selection state), per-row scale --------------------------------------------
-    int S3[NT];
-    u32x4v hq[2][NT][2];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        float m3 = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) m3 = absmax4(m3, hp[t][nt]);
-        m3 = row_max4(m3);
-        const int s3 = h2_scale(m3, -90, 90 - sw[3]);
-        S3[nt] = sw[3] + s3;
-        const float c3 = pow2f(s3);
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-            float v8[8];
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) v8[4 * c + v] = hp[2 * sl + c][nt][v];
-            split2s(v8, c3, hq[sl][nt][0], hq[sl][nt][1]);
-        }
-    }
-    float best[NT], un3[NT];
-    int bj[NT];
-    uint64_t amask[NT][2];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        best[nt] = -__builtin_inff();
-        bj[nt] = 0x7fffffff;
-        amask[nt][0] = amask[nt][1] = 0;
-        un3[nt] = pow2f(-S3[nt]);
-    }
-    int lane2 = lane;
-    // the rollout recomputes the lane's W2 address here each tile (hoisted, it was spilled and
-    // its reload waited for every store of the tile)
-    if (ALLAV) asm volatile("" : "+v"(lane2));
-    const lds_u4p W2s = (lds_u4p)(Wl + lds_w2_off(RNN, nct));
-    const u32x4v *W2g = a.pk + 1 + w1s_f4(a.g.Kp) + rec_f4(RNN);
-    for (int c0 = 0; c0 < nct; c0 += 4) {
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            const int c = c0 + cc;
-            if (c >= nct) break;
-            const int j0 = 16 * c + 4 * q;
-            uint32_t av[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const uint32_t w = avw[cc][nt];
-                av[nt] = ((w & 0xffu) != 0) | (((w >> 8) & 0xffu) != 0) << 1 | (((w >> 16) & 0xffu) != 0) << 2 |
-                         ((w >> 24) != 0) << 3;
-                if (c + 4 < nct) avw[cc][nt] = load_av(c + 4, nt);  // the ring: 4 tiles ahead
-            }
-            f32x4 a2[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) a2[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-                u32x4v w[2];
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    w[pl] = W2L ? W2s[w2_idx(c, sl, pl, lane2)] : W2g[w2_idx(c, sl, pl, lane2)];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) a2[nt] = mfma_h2(w, hq[sl][nt], a2[nt]);
-            }
-            const f32x4 bq = Bs[80 + 4 * c + q];  // b2[16 c + 4 q ..] (zero past n_out)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const f32x4 qv = a2[nt] * un3[nt] + bq;
-                if (a.Q && ok[nt]) {
-                    float *qp = a.Q + rows[nt] * nout + j0;
-                    if (!GEN) {
-                        *reinterpret_cast<float4 *>(qp) = make_float4(qv[0], qv[1], qv[2], qv[3]);
-                    } else {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                            if (j0 + v < nout) qp[v] = qv[v];
-                    }
-                }
-                if (SEL && ALLAV && !GEN) {
-                    // every task available and inside the row (the rollout at m % 32 == 0): the
-                    // lane's first task (c = 0, v = 0) is its first candidate, then strictly
-                    // greater or the first NaN -- the torch.max order below without the
-                    // availability / range terms
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int j = j0 + v;
-                        const float x = qv[v];
-                        const bool b = (c == 0 && v == 0) | ((best[nt] == best[nt]) & !(x <= best[nt]));
-                        best[nt] = b ? x : best[nt];
-                        bj[nt] = b ? j : bj[nt];
-                    }
-                } else if (SEL) {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        // a lane meets its tasks in increasing j, so torch.max order reduces
-                        // to: the first candidate, then strictly greater, or the first NaN
-                        const int j = j0 + v;
-                        const float x = ((av[nt] >> v) & 1u) ? qv[v] : -__builtin_inff();
-                        const bool b = ((bj[nt] == 0x7fffffff) & (j < nout)) |
-                                       ((best[nt] == best[nt]) & !(x <= best[nt]) & (j < nout));
-                        best[nt] = b ? x : best[nt];
-                        bj[nt] = b ? j : bj[nt];
-                    }
-                    amask[nt][0] |= (uint64_t)av[nt] << (4 * (c & 15));
-                }
-            }
-        }
-    }
-    if (SEL && ALLAV && !GEN) {
-        // the availability masks the exploration draw reads: every task of the lane's tiles
-        const uint64_t all = nct >= 16 ? ~0ull : ((1ull << (4 * nct)) - 1ull);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) amask[nt][0] = all;
-    }
-    if (SEL) {
-        const int act = select_finish<false, NT>(best, bj, amask, rows, ok, oidx, nct, sel, q);
-        const int nt = NT == 1 ? 0 : (q & 1);
-        if (act_lds && q < NT && ok[nt]) act_lds[lrow0 + 16 * nt + r] = (uint16_t)act;
-    }
-}
-
-// One wave, 32 agent rows of a flat [R][K] input: fc1 -> recurrent layer -> fc2 (+ selection).
-template <int NT, bool RNN, bool SEL, bool W2L, bool GEN, class A>
-__device__ __forceinline__ void agent_rows_h2(int64_t row0, A &a, const u32x4v *Wl, const int (&sw)[4]) {
-    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
-    if (row0 >= a.R) return;
-    auto &g = a.g;
-    int64_t rows[NT];
-    bool ok[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        rows[nt] = row0 + 16 * nt + r;
-        ok[nt] = rows[nt] < a.R;
-    }
-    const lds_f4v Bs = (lds_f4v)(Wl + rec_f4(RNN));
-    const u32x4v *W1g = a.pk + 1;
-    const float *xr[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) xr[nt] = a.X + (ok[nt] ? rows[nt] : 0) * a.xs;
-    const int Ub = g.Pp >> 5, nsl = g.Kp >> 5;
-    const int s0 = h2_s0(a);
-
-    // padded slice sl of every row: block sl / Ub, inputs 32 (sl % Ub) + 16 c + 4 q + e of it
-    auto load_x = [&](int sl, float4 (&xv)[2][NT]) {
-        if (!GEN) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    xv[c][nt] = *reinterpret_cast<const float4 *>(xr[nt] + 32 * sl + 16 * c + 4 * q);
-        } else {
-            const int blk = sl / Ub, jj0 = 32 * (sl - blk * Ub);
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int jj = jj0 + 16 * c + 4 * q;
-                    const float *p = xr[nt] + (int64_t)blk * g.P + jj;
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (ok[nt] && jj + e < g.P) ? p[e] : 0.f;
-                    xv[c][nt] = make_float4(v[0], v[1], v[2], v[3]);
-                }
-        }
-    };
-    // block 0 chunks t4 .. t4 + 3 (16 inputs each)
-    auto load_pa = [&](int t4, float4 (&pa)[4][NT]) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int jj = 16 * (t4 + c) + 4 * q;
-                if (t4 + c >= (g.Pp >> 4)) {
-                    pa[c][nt] = make_float4(0.f, 0.f, 0.f, 0.f);
-                } else if (!GEN) {
-                    pa[c][nt] = *reinterpret_cast<const float4 *>(xr[nt] + jj);
-                } else {
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = (ok[nt] && jj + e < g.P) ? xr[nt][jj + e] : 0.f;
-                    pa[c][nt] = make_float4(v[0], v[1], v[2], v[3]);
-                }
-            }
-    };
-    float4 pa[4][NT];
-    if (a.pre) load_pa(0, pa);
-    // main-loop slice order: with the prefix geometry (blocks 1 .. NB - 1 of Ub chunks), chunk
-    // u outer and block inner -- the order in which the rollout kernel generates them
-    const int nmain = nsl - s0;
-    const int nblk = g.NB - 1;
-    auto sl_of = [&](int idx) { return a.pre ? (idx % nblk + 1) * Ub + idx / nblk : idx; };
-    float4 xbuf[kH2XBuf][2][NT];
-#pragma unroll
-    for (int b = 0; b < kH2XBuf; ++b)
-        if (b < nmain) load_x(sl_of(b), xbuf[b]);
-
-    // ---- one-hot prefix: rows whose block 0 is onehot(a) or zero add W1[:, a] (W1T, f32)
-    // instead of running those slices' MFMAs
-    int pos[NT];
-    bool onehot = false;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) pos[nt] = -1;
-    if (a.pre) {
-        bool bad = false;
-        for (int t4 = 0; t4 < (g.Pp >> 4); t4 += 4) {
-            if (t4 > 0) load_pa(t4, pa);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = comp(pa[c][nt], e);
-                        const bool one = v == 1.0f;
-                        bad |= (one && pos[nt] >= 0) || (!one && v != 0.0f);
-                        pos[nt] = one ? 16 * (t4 + c) + 4 * q + e : pos[nt];
-                    }
-        }
-        bool rows_ok = true;  // a row's 1 may sit in only one of its 4 lanes
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const uint64_t mk = __ballot(pos[nt] >= 0);
-            const uint64_t g0 = mk & 0xffffull, g1 = (mk >> 16) & 0xffffull, g2 = (mk >> 32) & 0xffffull, g3 = mk >> 48;
-            rows_ok = rows_ok && ((g0 & g1) | (g0 & g2) | (g0 & g3) | (g1 & g2) | (g1 & g3) | (g2 & g3)) == 0;
-            int p = pos[nt];
-            p = max(p, __shfl_xor(p, 16));
-            p = max(p, __shfl_xor(p, 32));
-            pos[nt] = p;
-        }
-        onehot = rows_ok && __ballot(bad) == 0;
-    }
-    // ---- fc1 on split f16 MFMAs, per-row input scale ----------------------------------------
-    f32x4 acc[4][NT];
-    int sx[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) sx[nt] = kH2SxInit;
-    float4 hB[4][NT];
-    auto load_h = [&]() {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                hB[t][nt] = (RNN && a.Hin) ? *reinterpret_cast<const float4 *>(a.Hin + (ok[nt] ? rows[nt] : 0) * a.hs +
-                                                                              16 * t + 4 * q)
-                                           : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    for (int attempt = 0;; ++attempt) {
-        if (attempt > 0) {
-#pragma unroll
-            for (int b = 0; b < kH2XBuf; ++b)
-                if (b < nmain) load_x(sl_of(b), xbuf[b]);
-        }
-        float scx[NT], rmax[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            scx[nt] = pow2f(sx[nt]);
-            rmax[nt] = 0.f;
-            const float scS = pow2f(sw[0] + sx[nt]);
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const float4 gv = (onehot && pos[nt] >= 0)
-                                      ? *reinterpret_cast<const float4 *>(a.W1T + pos[nt] * kHid + 16 * mt + 4 * q)
-                                      : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc[mt][nt] = f32x4{gv.x, gv.y, gv.z, gv.w} * scS;
-            }
-        }
-        auto slice = [&](int sl, const float4 (&xv)[2][NT], bool lds) {
-            u32x4v xp[NT][2];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                rmax[nt] = absmax4(absmax4(rmax[nt], xv[0][nt]), xv[1][nt]);
-                const float x8[8] = {xv[0][nt].x, xv[0][nt].y, xv[0][nt].z, xv[0][nt].w,
-                                     xv[1][nt].x, xv[1][nt].y, xv[1][nt].z, xv[1][nt].w};
-                split2s(x8, scx[nt], xp[nt][0], xp[nt][1]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                u32x4v w[2];
-                if (lds) {
-                    const lds_u4p W1s = (lds_u4p)(Wl + lds_w1_off(RNN, g.nct, W2L));
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) w[pl] = W1s[w1_idx(sl - s0, mt, pl, lane)];
-                } else {
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) w[pl] = W1g[w1_idx(sl, mt, pl, lane)];
-                }
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma_h2(w, xp[nt], acc[mt][nt]);
-            }
-        };
-        // block 0 of a tile that is not one-hot: its slices through L2
-        for (int sl = 0; sl < ((a.pre && !onehot) ? s0 : 0); ++sl) {
-            float4 xv[2][NT];
-            load_x(sl, xv);
-            slice(sl, xv, false);
-        }
-        const int s_l2 = s0 + a.w1_lds;  // first slice read through L2
-        for (int i0 = 0; i0 < nmain; i0 += kH2XBuf) {
-#pragma unroll
-            for (int b = 0; b < kH2XBuf; ++b) {
-                if (i0 + b < nmain) {
-                    const int sl = sl_of(i0 + b);
-                    if (sl < s_l2) slice(sl, xbuf[b], true);
-                    else slice(sl, xbuf[b], false);
-                    if (i0 + b + kH2XBuf < nmain) load_x(sl_of(i0 + b + kH2XBuf), xbuf[b]);
-                }
-            }
-        }
-        if (attempt == 0 && RNN) load_h();  // after fc1: 32 fewer VGPRs live through it
-        // the split needs |x| 2^sx < 2^15 (|h| <= 65504): rows that overflow redo at their own
-        // smaller scale (the others keep theirs, so their values are unchanged)
-        bool over[NT], any = false;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float rm = row_max4(rmax[nt]);
-            over[nt] = rm * scx[nt] >= 32768.f;
-            any = any || over[nt];
-            if (over[nt]) sx[nt] = h2_scale(rm, -90, 90 - sw[0]);
-        }
-        if (attempt > 0 || __ballot(any) == 0) break;
-    }
-    f32x4 xB[4][NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const float un = pow2f(-(sw[0] + sx[nt]));
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const f32x4 bb = Bs[4 * mt + q];  // b1[16 mt + 4 q ..]
-#pragma unroll
-            for (int v = 0; v < 4; ++v) xB[mt][nt][v] = fmaxf(acc[mt][nt][v] * un + bb[v], 0.f);
-        }
-    }
-    h2_tail<NT, RNN, SEL, W2L, false, GEN>(a, Wl, sw, row0, rows, ok, hB, xB);
-}
-
-#ifndef ASG_H2_KARG
-#define ASG_H2_KARG 1
-#endif
 typedef __attribute__((address_space(4))) const H2Args KH2Args;
 // Persistent: one 512-thread workgroup per CU stages the LDS image, then its 8 waves walk
 // 256-row tiles.
@@ -845,19 +48,14 @@ rnn_agent_h2_kernel(H2Args a) {
     const int64_t ntiles = (a.R + kH2Waves * (16 * NT) - 1) / (kH2Waves * (16 * NT));
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = (tile * kH2Waves + (threadIdx.x >> 6)) * (16 * NT);
-#if ASG_H2_KARG
         // each tile re-reads the launch arguments (scalar loads): kept live from the kernel
         // entry they overflow the SGPR file (see rollout_args)
         KH2Args *p = (KH2Args *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(p));
         agent_rows_h2<NT, RNN, SEL, W2L, GEN>(row0, *p, s_h2, sw);
-#else
-        agent_rows_h2<NT, RNN, SEL, W2L, GEN>(row0, a, s_h2, sw);
-#endif
     }
 }
 
-#if !ASG_H2_TU
 // ---- packing: max|W| -> scale exponent, then the scaled f16 planes ------------------------
 __global__ void h2_exp_kernel(const float *W, int64_t n, int *out) {
     __shared__ float s_m[16];
@@ -933,30 +131,7 @@ hipError_t launch_h2_pack(const float *W1, const float *Wih, const float *Whh, c
     pack(W2, nout, kHid, kHid, kHid, g.nct, 2, 0, 3, o);
     return hipGetLastError();
 }
-#endif  // !ASG_H2_TU
 
-// LDS plan: recurrent planes, biases, W2 planes when they fit, then as many W1 slices (from
-// s0) as fit; `reserve` bytes per workgroup kept for a per-wave scratch
-struct H2Lds {
-    bool w2l;
-    int w1_lds, l2_slices;
-    int64_t scratch_off;  // u32x4v units
-    size_t bytes;
-};
-static inline H2Lds h2_lds_plan(const H2Geom &g, bool rnn, int s0, int64_t reserve_f4) {
-    constexpr int64_t kCap = 160 * 1024 / 16;
-    H2Lds p{};
-    p.w2l = lds_w2_off(rnn, g.nct) + w2s_f4(g.nct) + reserve_f4 <= kCap;
-    const int64_t w1off = lds_w1_off(rnn, g.nct, p.w2l);
-    const int64_t slices = g.Kp / 32 - s0, fit = (kCap - reserve_f4 - w1off) / (4 * 2 * 64);
-    p.w1_lds = (int)(fit < slices ? (fit > 0 ? fit : 0) : slices);
-    p.l2_slices = (int)(slices - p.w1_lds);
-    p.scratch_off = w1off + (int64_t)p.w1_lds * 4 * 2 * 64;
-    p.bytes = (size_t)(p.scratch_off + reserve_f4) * 16;
-    return p;
-}
-
-#if !ASG_H2_TU
 hipError_t launch_h2_agent(const float *X, int64_t xs, int64_t R, int K, const float *Hin, int64_t hs,
                            const float4 *packed, const float *b1, const float *bih, const float *bhh, const float *b2,
                            int nout, int use_rnn, float *Hout, float *Q, const SelectArgs *sel, hipStream_t s) {
@@ -1005,908 +180,7 @@ hipError_t launch_h2_agent(const float *X, int64_t xs, int64_t R, int K, const f
 #undef LH_
     return hipGetLastError();
 }
-#endif  // !ASG_H2_TU
 
-// =====================================================================================
-// Fused rollout (mock env, Philox bumps): for every env, transitions k0 .. k1 - 1 and the
-// agent forward + epsilon-greedy selection of the rows in between, in one launch.  One wave
-// per env (persistent over envs): the transition runs with lane = agent (collision counts,
-// float64 rewards summed in agent order, the env's previous / selected tasks and task scales
-// in the wave's LDS scratch -- never re-read from HBM); the env's 32-agent tiles then
-// generate the next observation row in the split-f16 MFMA operand layout (lane (r, q)
-// evaluates the Philox bumps of tasks 32 u + 16 c + 4 q + v), write it to the batch and feed
-// fc1 from registers: the agent never reads an observation back.  Selected tasks go to the
-// batch's actions row and to the LDS, where the next transition reads them.  The hidden
-// state lives in Hout between passes (Hin for the first).  Results are those of the separate
-// launches: asg_reset / asg_step rows, and the agent kernel's actions and hidden state
-// (per-row scales make a row's result independent of its tile's other rows).
-// =====================================================================================
-struct RolloutArgs {
-    // time-major batch: row 0 of each field ([T+1][E][..] storage: row t at base + t * E * ..,
-    // the row strides derived from E, n, m, K); NULL = absent
-    float *obs, *beta, *rew;
-    uint8_t *avail, *term;
-    int64_t *onehot, *act, *prevb, *filled;
-    int ts0;  // batch row of transition k0
-    // env state
-    int *prev;
-    double *returns;
-    const double *T_trans;
-    int *env_err;
-    double lambda_;
-    uint64_t seed;
-    int64_t env_base, E;
-    uint32_t episode, quirks;
-    int n, m, T, L, dense;
-    float wmin, wmax;
-    int k0, k1, select_first, select_last;
-    int reset;  // the envs' reset (asg_reset) runs first, in this launch
-    // benefits: NULL = Philox bumps regenerated in registers; else the handle's float64 table
-    // [E][T][n][m] (MT19937 compat / injected sat_prox_mat), read for the L lookahead rows
-    const double *table;   // injected float64 benefits (rewards), or
-    const double2 *par;    // the MT19937 reset's draws: rewards evaluated from them (mt_par_value)
-    const float *table32;  // the benefits rounded to float32: the lookahead rows' reads
-    // MT19937 draws: table32 is COMPACT (per (env, t) slice the bump pairs only, (agent, task)
-    // order; asg_env.hip:mt_table_kernel): their masks [E][n][W] and each word's first index
-    const uint64_t *tmask;
-    const int *toff;
-    // QOUT instances: the agent's Q rows [E n][m] f32 (the forward of asg_rnn_agent_forward)
-    // instead of the epsilon-greedy selection -- a selector outside the kernel (SAP) acts on them
-    float *Q;
-    // agent
-    const u32x4v *pk;
-    const float *W1T, *Hin;
-    int64_t hs;
-    float *Hout;
-    const float *b1, *bi, *bh, *b2;
-    int w1_lds, w1_off;  // LDS-resident W1 slices: [s0 + w1_off, s0 + w1_off + w1_lds)
-    float epsilon;
-    uint32_t sk0, sk1, counter;
-    int *sel_err;
-    int64_t scratch_off;  // per-wave LDS scratch (u32x4v units)
-    // bids_as_actions (asg_step_forward): the tasks of transition k0 are the handle's LSA
-    // assignments of the bids row [E][n] instead of the batch's actions row
-    const int *assign;
-};
-
-// The launch arguments as the tiles and transitions read them: a kernarg-segment pointer made
-// opaque per call, so each call re-reads what it uses with scalar loads instead of the kernel
-// keeping ~40 uniform values live from its entry (they overflowed the SGPR file and were spilled
-// to VGPR lanes, ~500 v_readlane reloads in the tile body).  ASG_ROLLOUT_KARG=0: the by-value
-// argument throughout (A/B).
-#ifndef ASG_ROLLOUT_KARG
-#define ASG_ROLLOUT_KARG 1
-#endif
-typedef __attribute__((address_space(4))) const RolloutArgs KRolloutArgs;
-__device__ __forceinline__ KRolloutArgs &rollout_args(KRolloutArgs *p) {
-    asm volatile("" : "+s"(p));
-    return *p;
-}
-
-__host__ __device__ inline int rollout_mp(int m) { return (m + 31) / 32 * 32; }
-__host__ __device__ inline int rollout_np(int n) { return (n + 31) / 32 * 32; }
-// per wave: task-scale bits [4] u64 | the env's return f64 | collision counts [mp] int |
-// selected / previous tasks [np] u16 each
-__host__ __device__ inline int rollout_scratch_bytes(int n, int m) {
-    return (40 + 4 * rollout_mp(m) + 4 * rollout_np(n) + 15) / 16 * 16;
-}
-
-// Orders one wave's LDS scratch accesses across its lanes (the collision counts, the actions /
-// previous tasks, the env's return).  A wave's LDS instructions complete in issue order, so a
-// wavefront-scope fence (compiler ordering, no wait) is enough.  ASG_LDS_FENCE_WG=1: the
-// round-4 workgroup-scope fence, whose release also waited for every outstanding global store
-// (s_waitcnt vmcnt(0)) -- three drains of the previous tile's row stores per transition (A/B)
-#ifndef ASG_LDS_FENCE_WG
-#define ASG_LDS_FENCE_WG 0
-#endif
-__device__ __forceinline__ void wave_lds_fence() {
-#if ASG_LDS_FENCE_WG
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
-}
-
-// 1: the n = m = 64 shape runs the compile-time-shape instances (0: the runtime-shape ones, A/B)
-#ifndef ASG_ROLLOUT_SQ64
-#define ASG_ROLLOUT_SQ64 1
-#endif
-// 1: the table modes (same-seed / injected) take the SQ64 instances too
-#ifndef ASG_ROLLOUT_SQ64_TAB
-#define ASG_ROLLOUT_SQ64_TAB 1
-#endif
-// 1: the SQ = 64 instances also fix L = 3 (launched only when L == 3): the unrolled lookahead
-// loop spills 28 VGPRs instead of 14 and ran 0.709-0.713 vs 0.570-0.574 ms/step (r5 A/B) -- off
-#ifndef ASG_SQ64_L3
-#define ASG_SQ64_L3 0
-#endif
-// The env shape as the rollout code reads it: SQ = 0 takes n, m from the launch arguments; the
-// SQ = 64 instances (n = m = 64, configs[2]'s shape) see them as compile-time constants, so the
-// tile's loops unroll and its row / task offsets fold into immediates
-template <int SQ, class RA>
-__device__ __forceinline__ int rs_n(RA &ra) { return SQ ? SQ : ra.n; }
-template <int SQ, class RA>
-__device__ __forceinline__ int rs_m(RA &ra) { return SQ ? SQ : ra.m; }
-// ... and L = 3 (configs[2]'s lookahead) when ASG_SQ64_L3: the lookahead loop unrolls
-template <int SQ, class RA>
-__device__ __forceinline__ int rs_L(RA &ra) { return (SQ && ASG_SQ64_L3) ? 3 : ra.L; }
-
-template <int SQ = 0, class RA>
-__device__ __forceinline__ H2Args rollout_h2args(RA &ra) {
-    H2Args a{};
-    const int n = rs_n<SQ>(ra), m = rs_m<SQ>(ra), L = rs_L<SQ>(ra);
-    a.R = ra.E * n;
-    a.g.K = m * (L + 1);
-    a.g.P = m;
-    a.g.NB = L + 1;
-    a.g.Pp = rollout_mp(m);
-    a.g.Kp = a.g.Pp * (L + 1);
-    a.g.prefix = 1;
-    a.g.nout = m;
-    a.g.nct = (m + 15) / 16;
-    a.pre = 1;
-    a.pk = ra.pk;
-    a.W1T = ra.W1T;
-    a.b1 = ra.b1;
-    a.bi = ra.bi;
-    a.bh = ra.bh;
-    a.b2 = ra.b2;
-    a.Hout = ra.Hout;
-    a.w1_lds = ra.w1_lds;
-    a.w1_off = ra.w1_off;
-    a.sel = SelectArgs{nullptr, 0, 0, n, ra.epsilon, ra.sk0, ra.sk1, ra.counter, ra.env_base * n, nullptr,
-                       (int64_t)n, 1, ra.sel_err};
-    return a;
-}
-
-__device__ __forceinline__ float task_scale(const uint64_t *s_scl, int j) {
-    return ((s_scl[j >> 6] >> (j & 63)) & 1ull) ? 10.0f : 1.0f;
-}
-
-// the launch's first transition without a selection before it: its tasks come from the
-// batch's actions row (read in the env prologue, so the transitions themselves issue no
-// global load -- a wait for one would drain the previous tile's stores every step)
-template <class RA>
-__device__ __forceinline__ void rollout_actions_from_batch(RA &ra, int64_t e, int ts, uint16_t *s_act) {
-    const int lane = threadIdx.x & 63;
-    const int n = ra.n, m = ra.m;
-    int err = 0;
-    for (int i = lane; i < n; i += 64) {
-        const int64_t a64 = ra.assign ? (int64_t)ra.assign[e * n + i] : ra.act[((int64_t)ts * ra.E + e) * n + i];
-        int a = (a64 >= 0 && a64 < m) ? (int)a64 : -1;
-        if (a < 0) err = ASG_E_ACTION_RANGE;
-        s_act[i] = (uint16_t)(a < 0 ? 0 : a);
-    }
-    err = wave_or_i32(err);
-    if (lane == 0 && err) atomicCAS(ra.env_err, 0, err);
-}
-
-// one transition (mock_constellation_env.py:116-162 + the runner's rows): rewards, returns,
-// terminated / filled / prev_assigns rows; the tasks come from the LDS (selected in this
-// launch, or read from the batch by the env prologue)
-template <int TAB, int SQ, class RA>
-__device__ __forceinline__ void rollout_transition(RA &ra, int64_t e, int k, int ts, const EnvKey &key,
-                                                   const uint64_t *s_scl, int *s_cnt, uint16_t *s_act,
-                                                   uint16_t *s_prev, double *s_ret) {
-    asm volatile("" : "+s"(e), "+s"(ts));
-    // the lane index is recomputed here, not kept across the step loop (spilled, its reload
-    // waited behind the previous tile's stores every step)
-    int lane_ = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane_));
-    const int lane = lane_;
-    const int n = rs_n<SQ>(ra), m = rs_m<SQ>(ra), mp = rollout_mp(m);
-    for (int j = lane; j < mp; j += 64) s_cnt[j] = 0;
-    wave_lds_fence();
-    for (int i = lane; i < n; i += 64) atomicAdd(&s_cnt[s_act[i]], 1);
-    wave_lds_fence();
-    const BumpShape bsh = bump_shape(ra.T, ra.wmin, ra.wmax);
-    (void)bsh;
-    double sum = 0.0;  // Python's sum(rewards), left to right: lane order within each 64-agent chunk
-    // two copies of the loop, with and without an injected T_trans: merged, the join after
-    // the table load made every transition wait for the previous tile's stores (vmcnt)
-    auto rewards = [&](auto with_table) {
-        constexpr bool TT = decltype(with_table)::value;
-        for (int i0 = 0; i0 < n; i0 += 64) {
-            const int i = i0 + lane;
-            double rr = 0.0;
-            if (i < n) {
-                const int j = s_act[i], p = s_prev[i];
-                double beta;
-                if constexpr (TAB) {
-                    beta = ra.par ? mt_par_value(ra.par[(e * m + j) * n + i], k)
-                                  : ra.table[(((int64_t)e * ra.T + k) * n + i) * m + j];
-                } else if (ASG_ROLLOUT_XSKIP & 1024) {
-                    beta = (double)(j & 3) * 0.25;
-                } else {
-                    const Bump32 b =
-                        philox_bump32(key, ra.episode, i * m + j, task_scale(s_scl, j), bsh, ra.dense != 0);
-                    beta = bump64_at(b, k);
-                }
-                const double tt = TT ? ra.T_trans[(int64_t)p * m + j] : (j == p ? 0.0 : 1.0);
-                const double pen = tt * (beta > 1e-12 ? 1.0 : 0.0);
-                const double bh = beta - ra.lambda_ * pen;
-                rr = bh > 0.0 ? bh / (double)s_cnt[j] : bh;
-                if (ra.rew) ra.rew[((int64_t)ts * ra.E + e) * n + i] = (float)rr;
-                s_prev[i] = (uint16_t)j;
-                if (ra.prevb)
-                    ra.prevb[((int64_t)(ts + 1) * ra.E + e) * n + i] =
-                        (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : j;
-            }
-            const int lo = __double2loint(rr), hi = __double2hiint(rr);
-            const int cnt = n - i0 < 64 ? n - i0 : 64;
-            for (int l2 = 0; l2 < ((ASG_ROLLOUT_XSKIP & 512) ? 1 : cnt); ++l2)
-                sum += __hiloint2double(__builtin_amdgcn_readlane(hi, l2), __builtin_amdgcn_readlane(lo, l2));
-        }
-    };
-    if (ra.T_trans) rewards(std::true_type{});
-    else rewards(std::false_type{});
-    if (lane == 0) {
-        *s_ret += sum;  // the return lives in LDS: a register copy spilled, its reload drained the stores
-        bool term = k + 1 >= ra.T;  // terminated = done != info.get("T", False)
-        if (ra.quirks & ASG_QUIRK_PARALLEL_TERMINATED) term = (e != 0);
-        if (ra.term) ra.term[(int64_t)ts * ra.E + e] = term;
-        if (ra.filled) ra.filled[(int64_t)(ts + 1) * ra.E + e] = 1;
-    }
-    wave_lds_fence();
-}
-
-__device__ __forceinline__ void st_f4(float *p, float a, float b, float c, float d) {
-    *reinterpret_cast<f32x4 *>(p) = f32x4{a, b, c, d};
-}
-__device__ __forceinline__ void st_i64x2(int64_t *p, long long a, long long b) {
-    *reinterpret_cast<i64x2v *>(p) = i64x2v{a, b};
-}
-
-// One 32-agent tile of env e for observation row kk (batch row tsr): write the row (STORES:
-// one-hot block and actions_onehot of the transition before it, avail, lookahead blocks,
-// beta) and, AGENT, run fc1 on the generated blocks plus the recurrent layer, fc2 and the
-// selection of row kk.  have_act: block 0 is onehot(s_act) (else zeros: the reset row).
-// The agent tile's h_t rows (RNN): hN holds them on entry when the previous agent tile
-// prefetched them (hpf), else they are loaded at the tile start; either way they are waited
-// for with the one-hot gather, before the tile's stores (a wait after fc1 would drain every
-// store of the tile: gfx9's vmcnt retires memory operations in order).  After the recurrent
-// layer the tile issues the NEXT agent tile's h_t loads into hN (nsrc: its source rows, row
-// nrow0 on, stride nhs; NULL source = zeros; nmode 0 = no next agent tile in this env).
-// The compact same-seed table (RolloutArgs::tmask): the 4 tasks j0 .. j0 + 3 of a row (j0 % 4 == 0,
-// one mask word) are the set bits `nib` of the row's mask word at sh = j0 % 64, and their values
-// sit at consecutive compact indices from pos = the word's first index + the bumps below sh.  One
-// 16-byte load at pos (4-byte aligned; nib == 0: no load) then the expansion below
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-__device__ __forceinline__ f32x4 compact_quad_load(const float *slice, uint64_t mw, int off, int sh, bool okrow,
-                                                   uint32_t *nib_out) {
-    const uint32_t nib = okrow ? (uint32_t)(mw >> sh) & 15u : 0u;
-    *nib_out = nib;
-    if (nib == 0u) return f32x4{0.f, 0.f, 0.f, 0.f};
-    const int pos = off + (int)__popcll(mw & ((1ull << sh) - 1ull));
-    if (ASG_ROLLOUT_XSKIP & 2048) return f32x4{0.5f, 0.25f, 0.125f, (float)pos};
-    const f32x4u x = *reinterpret_cast<const f32x4u *>(slice + pos);
-    return f32x4{x.x, x.y, x.z, x.w};
-}
-__device__ __forceinline__ uint32_t compact_nib(uint64_t mw, int sh, bool okrow) {
-    return okrow ? (uint32_t)(mw >> sh) & 15u : 0u;
-}
-// the quad's 4 values from its packed bumps x (value v = the (rank of v)-th packed one, 0 off the mask)
-__device__ __forceinline__ float4 compact_expand(f32x4 x, uint32_t nib) {
-    if (ASG_ROLLOUT_XSKIP & 4096) return make_float4(x.x, x.y, x.z, x.w + (float)nib);
-    const bool b0 = nib & 1u, b1 = nib & 2u, b2 = nib & 4u, b3 = nib & 8u;
-    const float a01 = b0 ? x.y : x.x, a12 = b0 ? x.z : x.y, a23 = b0 ? x.w : x.z;  // rank shifted by b0
-    const float r2 = b1 ? a12 : a01;                                               // rank b0 + b1
-    const float r3 = b2 ? (b1 ? a23 : a12) : (b1 ? a12 : a01);                     // rank b0 + b1 + b2
-    return make_float4(b0 ? x.x : 0.f, b1 ? a01 : 0.f, b2 ? r2 : 0.f, b3 ? r3 : 0.f);
-}
-
-struct HNext {
-    const float *src;
-    int64_t stride, row0;
-    int mode;
-};
-
-// 1: with W2 in LDS and an fc1 slice in L2 (64 x 64: 1 of 6; the SQ64 instances), that slice is
-// the tile's first (0: the last one, its weights read behind nearly all the tile's stores --
-// round 4): 0.556-0.559 vs 0.575 ms/step (runtime-shape instances) on one box (r5 A/B); its rows
-// stored after its MFMAs as well spilled 43 VGPRs and ran 0.65 ms)
-#ifndef ASG_ROLLOUT_L2FIRST
-#define ASG_ROLLOUT_L2FIRST 1
-#endif
-// 1: the table modes load each chunk's first kTabPre lookahead blocks at the chunk start
-#ifndef ASG_TAB_PRELOAD
-#define ASG_TAB_PRELOAD 1
-#endif
-#ifndef ASG_TAB_PRE
-#define ASG_TAB_PRE 2
-#endif
-constexpr int kTabPre = ASG_TAB_PRE;  // lookahead blocks preloaded per chunk (the dense table)
-// the compact table (MT19937 draws): 1 block (SQ64 GRU instance: 0 VGPRs spilled, 51 with 2, 84
-// with 3; the dense instance: 36 / 19 / 36)
-#ifndef ASG_TAB_PRE_CMP
-#define ASG_TAB_PRE_CMP 1
-#endif
-#ifndef ASG_ROLLOUT_LATE
-#define ASG_ROLLOUT_LATE 1
-#endif
-template <bool RNN, bool W2L, bool GEN, int TAB, bool QOUT, bool AGENT, int SQ, class RA>
-__device__ __forceinline__ void rollout_tile(RA &ra, int64_t e, int sub, int kk, int tsr, bool stores,
-                                             bool have_act, int pass, const EnvKey &key, const uint64_t *s_scl,
-                                             uint16_t *s_act, const u32x4v *Wl, const int (&sw)[4],
-                                             f32x4 (&hN)[4][kH2NT], bool hpf, HNext nx) {
-    constexpr int NT = kH2NT;
-    constexpr int RT = 16 * NT;  // rows per tile
-    // opaque env / row indices and lane: addresses are formed here from them, not hoisted out
-    // of the step and env loops (live across every tile they spill)
-    asm volatile("" : "+s"(e), "+s"(tsr), "+s"(kk));
-    int lane_ = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane_));
-    const int lane = lane_, r = lane & 15, q = lane >> 4;
-    const int n = rs_n<SQ>(ra), m = rs_m<SQ>(ra), T = ra.T, L = rs_L<SQ>(ra);
-    const int K = m * (L + 1);
-    const int Ub = rollout_mp(m) >> 5;
-    const int64_t row0 = e * n + RT * sub;
-    int64_t rows[NT];
-    bool ok[NT];
-    int ia[NT], act[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        ia[nt] = RT * sub + 16 * nt + r;
-        ok[nt] = !GEN || ia[nt] < n;
-        rows[nt] = e * n + ia[nt];
-        act[nt] = (have_act && ok[nt]) ? (int)s_act[ia[nt]] : -1;
-    }
-    // the compact same-seed table's mask words / offsets of the lane's rows (chunk u's word is
-    // u / 2): loaded here, with the gather, before the tile's stores -- once per tile when the
-    // shape is compile-time 64 tasks (one word), per chunk otherwise
-    constexpr bool cmp = TAB == 2;  // the compact same-seed table (MT19937 draws)
-    uint64_t cmw[NT];
-    int cof[NT];
-    auto load_cm = [&](int w) {
-        const int W = (m + 63) >> 6;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int64_t r = (e * n + (ok[nt] ? ia[nt] : 0)) * W + w;
-            cmw[nt] = cmp ? ra.tmask[r] : 0ull;
-            cof[nt] = cmp ? ra.toff[r] : 0;
-        }
-    };
-    if (cmp && SQ == 64) load_cm(0);
-    // row stores: batch row tsr (timing variant 32: row 1, env e & 7)
-    const int tss = (ASG_ROLLOUT_XSKIP & 32) ? 1 : tsr;
-    const int64_t sro = (ASG_ROLLOUT_XSKIP & 32) ? ((e & 7) - e) * n : 0;
-    float *obs_r = ra.obs + ((int64_t)tss * ra.E * n + sro) * K;
-    // fc1 accumulators start from the one-hot block's W1 columns, gathered (and consumed)
-    // before the tile's stores (a load behind them would wait for their acknowledgements:
-    // gfx9's vmcnt retires memory operations in order); a rescaled retry gathers again
-    f32x4 acc[4][NT];
-    int sx[NT];
-    if (AGENT) {
-        const float scS = pow2f(sw[0] + kH2SxInit);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            sx[nt] = kH2SxInit;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const float4 g = (act[nt] >= 0 && !(ASG_ROLLOUT_XSKIP & 2))
-                                     ? *reinterpret_cast<const float4 *>(ra.W1T + act[nt] * kHid + 16 * mt + 4 * q)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc[mt][nt] = f32x4{g.x, g.y, g.z, g.w} * scS;
-            }
-        }
-    }
-    if (AGENT && RNN) {
-        if (!hpf) {
-            const float *hin = pass == 0 ? ra.Hin : ra.Hout;
-            const int64_t hs = pass == 0 ? ra.hs : kHid;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    hN[t][nt] = hin ? *reinterpret_cast<const f32x4 *>(hin + (ok[nt] ? rows[nt] : 0) * hs + 16 * t + 4 * q)
-                                    : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        // waited for here, with the gather
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(hN[t][nt]));
-    }
-    // w1_off (the SQ64 instances): the L2-resident fc1 slice is the tile's FIRST main slice, so
-    // the wait for its weights covers only the prefix rows and the first block's rows of the
-    // tile -- as the last slice (round 4) it waited for nearly all of the tile's stores
-    if (stores && !(ASG_ROLLOUT_XSKIP & 1)) {
-        // obs block 0 = onehot(a) (row kk), actions_onehot (row kk - 1), avail = 1 (row kk)
-        // actions_onehot of the transition before the row (none before the reset row)
-        int64_t *oh_r = (ra.onehot && have_act) ? ra.onehot + ((int64_t)(tss - 1) * ra.E * n + sro) * m : nullptr;
-        for (int u = 0; u < Ub; ++u)
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int j0 = 32 * u + 16 * c + 4 * q;
-                    const int aa = act[nt];
-                    if (!GEN) {
-                        st_f4(obs_r + rows[nt] * K + j0, aa == j0, aa == j0 + 1, aa == j0 + 2, aa == j0 + 3);
-                        if (oh_r) {
-                            st_i64x2(oh_r + rows[nt] * m + j0, aa == j0, aa == j0 + 1);
-                            st_i64x2(oh_r + rows[nt] * m + j0 + 2, aa == j0 + 2, aa == j0 + 3);
-                        }
-                    } else if (ok[nt]) {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                            if (j0 + v < m) {
-                                obs_r[rows[nt] * K + j0 + v] = aa == j0 + v ? 1.0f : 0.0f;
-                                if (oh_r) oh_r[rows[nt] * m + j0 + v] = aa == j0 + v;
-                            }
-                    }
-                }
-        if (ra.avail) {
-            uint8_t *ab = ra.avail + ((int64_t)tss * ra.E * n + sro + row0) * m;
-            const int nrow = GEN ? min(RT, n - RT * sub) : RT;
-            int off0 = (GEN ? 1 : 16) * lane;
-            asm volatile("" : "+v"(off0));  // not hoisted: a per-lane 64-bit address kept across loops spilled
-            if (!GEN) {
-                for (int off = off0; off < RT * m; off += 64 * 16)
-                    *reinterpret_cast<uint4 *>(ab + off) = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
-            } else {
-                for (int off = off0; off < nrow * m; off += 64) ab[off] = 1;
-            }
-        }
-    }
-    // ---- the lookahead blocks 1..L (times kk .. kk + L - 1), fc1 on them -------------------
-    BumpShape bsh = bump_shape(T, ra.wmin, ra.wmax);
-    bsh.q = __builtin_amdgcn_readfirstlane(bsh.q);  // uniform: keep the grid exponent scalar
-    const lds_f4v Bs = (lds_f4v)(Wl + rec_f4(RNN));
-    const u32x4v *W1g = ra.pk + 1;
-    const int s0 = Ub, s_l2 = s0 + ra.w1_off + ra.w1_lds;
-    float *beta_r = ra.beta ? ra.beta + ((int64_t)tss * ra.E * n + sro) * m : nullptr;
-    const bool live = kk < T;  // rows past T are zeros: no bump parameters needed
-    for (int attempt = 0;; ++attempt) {
-        float scx[NT], rmax[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            scx[nt] = pow2f(AGENT ? sx[nt] : 0);
-            rmax[nt] = 0.f;
-        }
-        if (AGENT && attempt > 0) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const float scS = pow2f(sw[0] + sx[nt]);
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const float4 g = act[nt] >= 0
-                                         ? *reinterpret_cast<const float4 *>(ra.W1T + act[nt] * kHid + 16 * mt + 4 * q)
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
-                    acc[mt][nt] = f32x4{g.x, g.y, g.z, g.w} * scS;
-                }
-            }
-        }
-        const bool st_now = stores && attempt == 0 && !(ASG_ROLLOUT_XSKIP & 1);
-        for (int u = 0; u < Ub; ++u) {
-            // bump parameters of the lane's 16 (row, task) pairs of this chunk (Philox mode)
-            Bump32 bp[2][4][NT];
-            // table modes: the chunk's lookahead values of the first kTabPre blocks, loaded at
-            // once at the chunk start (in place of the Philox parameters): one wait behind the
-            // tile's stores per chunk instead of one per block (gfx9's in-order vmcnt)
-            constexpr int kPre = TAB == 2 ? ASG_TAB_PRE_CMP : kTabPre;
-            float4 tv[kPre][2][NT];
-            if (cmp && SQ != 64) load_cm(u >> 1);
-            if constexpr (TAB && ASG_TAB_PRELOAD) {
-#pragma unroll
-                for (int l = 1; l <= kPre; ++l) {
-                    const int t = kk + l - 1;
-                    if (l > L || t >= T) continue;
-                    const float *trow = ra.table32 + ((int64_t)e * T + t) * n * m;
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const int j0 = 32 * u + 16 * c + 4 * q;
-                            const float *tp = trow + (int64_t)ia[nt] * m + j0;
-                            if constexpr (cmp) {  // the packed bumps: expanded at their use
-                                uint32_t nb;
-                                const f32x4 x = compact_quad_load(trow, cmw[nt], cof[nt], j0 & 63, ok[nt] && j0 < m, &nb);
-                                tv[l - 1][c][nt] = make_float4(x.x, x.y, x.z, x.w);
-                            } else if (!GEN) {
-                                tv[l - 1][c][nt] = *reinterpret_cast<const float4 *>(tp);
-                            } else {
-                                float v4[4];
-#pragma unroll
-                                for (int v = 0; v < 4; ++v) v4[v] = (ok[nt] && j0 + v < m) ? tp[v] : 0.f;
-                                tv[l - 1][c][nt] = make_float4(v4[0], v4[1], v4[2], v4[3]);
-                            }
-                        }
-                }
-            }
-            if constexpr (!TAB) {
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int jw = 32 * u + 16 * c + 4 * q;
-                const uint64_t sbits = s_scl[jw >> 6];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    if (!live) {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) bp[c][v][nt] = Bump32{0.f, 0.f, 0.f};
-                    } else if (ASG_ROLLOUT_XSKIP & 64) {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                            bp[c][v][nt] = Bump32{1.0f, (float)((jw + v + ia[nt]) & 15), 0.25f};
-                    } else if (!GEN) {
-                        // the lane's 4 pairs (j .. j + 3) are one Philox call (m % 4 == 0); their task
-                        // scales from one 4-bit field of the scale bits (jw % 4 == 0: no wrap), each
-                        // 1.0f or 10.0f as bits (0x3f800000 + b 0x01a00000)
-                        float sv[4];
-                        const uint32_t nib = (uint32_t)(sbits >> (jw & 63)) & 15u;
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) sv[v] = __builtin_bit_cast(float, 0x3f800000u + ((nib >> v) & 1u) * 0x01a00000u);
-                        Bump32 b4[4];
-                        philox_bump32x4(key, ra.episode, ia[nt] * m + jw, sv, bsh, ra.dense != 0, b4);
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) bp[c][v][nt] = b4[v];
-                    } else {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) {
-                            const int j = jw + v;
-                            const bool in = j < m;
-                            const float sv = ((sbits >> (j & 63)) & 1ull) ? 10.0f : 1.0f;
-                            bp[c][v][nt] = philox_bump32(key, ra.episode, ia[nt] * m + (in ? j : 0), sv, bsh,
-                                                         ra.dense != 0);
-                            if (!in) bp[c][v][nt].scale = 0.f;
-                        }
-                    }
-                }
-            }
-            }
-            for (int l = 1; l <= L; ++l) {
-                const int t = kk + l - 1;
-
-                // the 2 x NT x 4 bump values, straight-line (one uniform branch per block: rows
-                // past T are zeros)
-                float4 xv[2][NT];
-                if (TAB && ASG_TAB_PRELOAD && t < T && l <= kPre) {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            // l is a loop variable: the preloaded block by a uniform select
-                            float4 x = tv[0][c][nt];
-#pragma unroll
-                            for (int ll = 2; ll <= kPre; ++ll) x = l == ll ? tv[ll - 1][c][nt] : x;
-                            if constexpr (cmp) {
-                                const int j0 = 32 * u + 16 * c + 4 * q;
-                                x = compact_expand(f32x4{x.x, x.y, x.z, x.w},
-                                                   compact_nib(cmw[nt], j0 & 63, ok[nt] && j0 < m));
-                            }
-                            xv[c][nt] = x;
-                        }
-                } else if (TAB && t < T) {
-                    // the table's benefits rounded to float32 (the batch's dtype, as the separate
-                    // step's rows), from its float32 copy: B[e][t][row][j0 .. j0 + 3], one 16-byte
-                    // load (the float64 table would take two behind the tile's stores)
-                    const float *trow = ra.table32 + ((int64_t)e * T + t) * n * m;
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const int j0 = 32 * u + 16 * c + 4 * q;
-                            const float *tp = trow + (int64_t)ia[nt] * m + j0;
-                            if constexpr (cmp) {
-                                uint32_t nb;
-                                const f32x4 x = compact_quad_load(trow, cmw[nt], cof[nt], j0 & 63, ok[nt] && j0 < m, &nb);
-                                xv[c][nt] = compact_expand(x, nb);
-                            } else if (!GEN) {
-                                xv[c][nt] = *reinterpret_cast<const float4 *>(tp);
-                            } else {
-                                float v4[4];
-#pragma unroll
-                                for (int v = 0; v < 4; ++v) v4[v] = (ok[nt] && j0 + v < m) ? tp[v] : 0.f;
-                                xv[c][nt] = make_float4(v4[0], v4[1], v4[2], v4[3]);
-                            }
-                        }
-                } else if (!TAB && t < T) {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            xv[c][nt] = make_float4(bump32_at(bp[c][0][nt], t), bump32_at(bp[c][1][nt], t),
-                                                    bump32_at(bp[c][2][nt], t), bump32_at(bp[c][3][nt], t));
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) xv[c][nt] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                auto store_rows = [&]() {
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const float vv[4] = {xv[c][nt].x, xv[c][nt].y, xv[c][nt].z, xv[c][nt].w};
-                            const int j0 = 32 * u + 16 * c + 4 * q;
-                            if (!GEN) {
-                                st_f4(obs_r + rows[nt] * K + m * l + j0, vv[0], vv[1], vv[2], vv[3]);
-                                if (l == 1 && beta_r) st_f4(beta_r + rows[nt] * m + j0, vv[0], vv[1], vv[2], vv[3]);
-                            } else if (ok[nt]) {
-#pragma unroll
-                                for (int v = 0; v < 4; ++v)
-                                    if (j0 + v < m) {
-                                        obs_r[rows[nt] * K + m * l + j0 + v] = vv[v];
-                                        if (l == 1 && beta_r) beta_r[rows[nt] * m + j0 + v] = vv[v];
-                                    }
-                            }
-                        }
-                };
-                // an L2 weight slice (no W2 in LDS: the large shapes, 19 of 24 slices at 256 x 256):
-                // its weights are loaded before this block's row stores and the stores follow the
-                // MFMAs, so the loads wait for the previous block's stores only
-                const bool late = ASG_ROLLOUT_LATE && !W2L && AGENT && l * Ub + u >= s_l2;
-                if (st_now && !late) store_rows();
-                if (AGENT) {
-                    // the agent kernel's slice: abs-max, split, 4 output tiles x NT rows of MFMAs
-                    const int sl = l * Ub + u;
-                    u32x4v xp[NT][2];
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        rmax[nt] = absmax4(absmax4(rmax[nt], xv[0][nt]), xv[1][nt]);
-                        const float x8[8] = {xv[0][nt].x, xv[0][nt].y, xv[0][nt].z, xv[0][nt].w,
-                                             xv[1][nt].x, xv[1][nt].y, xv[1][nt].z, xv[1][nt].w};
-                        split2s(x8, scx[nt], xp[nt][0], xp[nt][1]);
-                    }
-                    // two copies of the MFMA block: merged after an LDS-or-global select, the
-                    // MFMAs would wait for vmcnt(0) -- every store of the tile -- each slice
-                    auto mma = [&](bool lds) {
-#pragma unroll
-                        for (int mt = 0; mt < 4; ++mt) {
-                            u32x4v w[2];
-                            if (lds) {
-                                const lds_u4p W1s = (lds_u4p)(Wl + lds_w1_off(RNN, (m + 15) / 16, W2L));
-#pragma unroll
-                                for (int pl = 0; pl < 2; ++pl)
-                                    w[pl] = W1s[w1_idx((ASG_ROLLOUT_XSKIP & 4) && sl >= s_l2 ? 0 : sl - s0 - ra.w1_off, mt,
-                                                       pl, lane)];
-                            } else {
-#pragma unroll
-                                for (int pl = 0; pl < 2; ++pl) w[pl] = W1g[w1_idx(sl, mt, pl, lane)];
-                            }
-#pragma unroll
-                            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma_h2(w, xp[nt], acc[mt][nt]);
-                        }
-                    };
-                    if ((sl >= s0 + ra.w1_off && sl < s_l2) || (ASG_ROLLOUT_XSKIP & 4))
-                        mma(true);
-                    else
-                        mma(false);
-                }
-                if (st_now && late) store_rows();
-            }
-        }
-        if (!AGENT) return;
-        bool over[NT], any = false;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float rm = row_max4(rmax[nt]);
-            over[nt] = rm * scx[nt] >= 32768.f;
-            any = any || over[nt];
-            if (over[nt]) sx[nt] = h2_scale(rm, -90, 90 - sw[0]);
-        }
-        if (attempt > 0 || __ballot(any) == 0) break;
-    }
-    if constexpr (AGENT) {
-        H2Args a = rollout_h2args<SQ>(ra);
-        a.sel.counter = ra.counter + (uint32_t)pass;
-        a.sel.out = ra.act + (int64_t)tsr * ra.E * n;
-        if constexpr (QOUT) a.Q = ra.Q;
-        float4 hB[4][NT];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                hB[t][nt] = (ASG_ROLLOUT_XSKIP & 8) ? make_float4(0.5f, 0.25f, -0.5f, 0.125f)
-                            : RNN ? make_float4(hN[t][nt][0], hN[t][nt][1], hN[t][nt][2], hN[t][nt][3])
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-        f32x4 xB[4][NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const float un = pow2f(-(sw[0] + sx[nt]));
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const f32x4 bb = Bs[4 * mt + q];
-#pragma unroll
-                for (int v = 0; v < 4; ++v) xB[mt][nt][v] = fmaxf(acc[mt][nt][v] * un + bb[v], 0.f);
-            }
-        }
-        // the next agent tile's h_t, issued once this tile's recurrent layer is done
-        auto prefetch = [&]() {
-            if (!RNN || nx.mode == 0) return;
-            const int64_t nb = e * n + nx.row0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int ni = (int)nx.row0 + 16 * nt + r;
-                    const bool nok = !GEN || ni < n;
-                    hN[t][nt] = nx.src ? *reinterpret_cast<const f32x4 *>(nx.src + (nok ? nb + 16 * nt + r : 0) * nx.stride +
-                                                                        16 * t + 4 * q)
-                                       : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-        };
-        h2_tail<NT, RNN, !QOUT, W2L, true, GEN>(a, Wl, sw, row0, rows, ok, hB, xB, s_act, RT * sub, prefetch);
-    }
-}
-
-template <bool RNN, bool W2L, bool GEN, int TAB, bool QOUT, int SQ>
-__global__ void __launch_bounds__(64 * kH2Waves) __attribute__((amdgpu_waves_per_eu(kH2WavesPerSimd)))
-rollout_kernel(RolloutArgs ra) {
-    extern __shared__ u32x4v s_h2[];
-    int sw[4];
-    h2_stage<RNN, W2L>(rollout_h2args(ra), s_h2, sw);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int n = rs_n<SQ>(ra), m = rs_m<SQ>(ra), mp = rollout_mp(m), np = rollout_np(n);
-    char *scr = reinterpret_cast<char *>(s_h2 + ra.scratch_off) + wv * rollout_scratch_bytes(n, m);
-    uint64_t *s_scl = reinterpret_cast<uint64_t *>(scr);
-    double *s_ret = reinterpret_cast<double *>(scr + 32);
-    int *s_cnt = reinterpret_cast<int *>(scr + 40);
-    uint16_t *s_act = reinterpret_cast<uint16_t *>(s_cnt + mp);
-    uint16_t *s_prev = s_act + np;
-    const int ntile = np / (16 * kH2NT);
-    const int64_t GW = (int64_t)gridDim.x * kH2Waves;
-    for (int64_t e0 = (int64_t)blockIdx.x * kH2Waves + wv; e0 < ra.E; e0 += GW) {
-        // addresses are recomputed from e each env: strength-reduced per-lane pointers carried
-        // across the env loop were spilled around the tile loop, and their reloads waited for
-        // every store of the env
-        int64_t e = e0;
-        asm volatile("" : "+s"(e));
-        const EnvKey key = env_key(ra.seed, ra.env_base + e);
-        // task scales (choice([1, 1, 1, 10]) per task) as bits (Philox mode), the env's
-        // previous tasks
-        for (int c = 0; c < (TAB ? 0 : (mp + 63) / 64); ++c) {
-            const int j = 64 * c + lane;
-            const bool ten = j < m && philox_task_scale(key, ra.episode, j) == 10.0f;
-            const uint64_t bits = __ballot(ten);
-            if (lane == 0) s_scl[c] = bits;
-        }
-        if (!TAB && ra.reset) {
-            // asg_reset (reset_kernel): prev_assigns = the first n of a Philox Fisher-Yates
-            // permutation of the m tasks (choice(m, n, replace=False), mock :99-105), drawn
-            // from the top; the draws are independent of the permutation, so the lanes make
-            // them in parallel and one lane applies the swaps (u16 halves of s_cnt: perm, draw)
-            uint16_t *s_perm = reinterpret_cast<uint16_t *>(s_cnt), *s_jj = s_perm + mp;
-            for (int j = lane; j < m; j += 64) {
-                s_perm[j] = (uint16_t)j;
-                const u32x4 rr = philox4x32_10(u32x4{(uint32_t)j, 0u, kCtrPerm, ra.episode}, key.k0, key.k1);
-                s_jj[j] = (uint16_t)(((uint64_t)rr.x * (uint64_t)(j + 1)) >> 32);
-            }
-            wave_lds_fence();
-            if (lane == 0)
-                for (int i = m - 1; i >= 1; --i) {
-                    const int jj = s_jj[i];
-                    const uint16_t t = s_perm[i];
-                    s_perm[i] = s_perm[jj];
-                    s_perm[jj] = t;
-                }
-            wave_lds_fence();
-            for (int i = lane; i < np; i += 64) {
-                const int p = i < n ? (int)s_perm[i] : 0;
-                s_prev[i] = (uint16_t)p;
-                s_act[i] = 0;
-                if (i < n && ra.prevb)
-                    ra.prevb[((int64_t)ra.ts0 * ra.E + e) * n + i] = (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : p;
-            }
-            if (lane == 0 && ra.filled) ra.filled[(int64_t)ra.ts0 * ra.E + e] = 1;
-        } else {
-            for (int i = lane; i < np; i += 64) {
-                const int p = i < n ? ra.prev[e * n + i] : 0;
-                s_prev[i] = (uint16_t)p;
-                s_act[i] = 0;
-                // table modes' reset in this launch: the permutation the reset's draw kernel
-                // left in prev; the reset row's prev_assigns / filled here, its obs by the tiles
-                if (TAB && ra.reset && i < n && ra.prevb)
-                    ra.prevb[((int64_t)ra.ts0 * ra.E + e) * n + i] = (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : p;
-            }
-            if (TAB && ra.reset && lane == 0 && ra.filled) ra.filled[(int64_t)ra.ts0 * ra.E + e] = 1;
-        }
-        if (lane == 0) *s_ret = ra.reset ? 0.0 : ra.returns[e];
-        if (!ra.select_first) rollout_actions_from_batch(ra, e, ra.ts0, s_act);
-        wave_lds_fence();
-        // iteration 0 with select_first: the selection on the reset row (no transition);
-        // every other iteration: transition k, then the agent tiles of row k + 1 (or, past the
-        // launch's last selection, the row alone) -- one call site per tile kind
-#if ASG_ROLLOUT_KARG
-        KRolloutArgs *const kra = (KRolloutArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-#define RA_ rollout_args(kra)
-#else
-#define RA_ ra
-#endif
-        const int sf = ra.select_first ? 1 : 0;
-        const int nit = ra.k1 - ra.k0 + sf;
-        int pass = 0;
-        f32x4 hN[4][kH2NT];  // the next agent tile's h_t rows (prefetched by the tile before it)
-        bool hpf = false;
-        auto has_agent = [&](auto &rr, int it) {
-            const int kk = rr.k0 + it - sf + 1;
-            return it < nit && kk < rr.T && (kk < rr.k1 || rr.select_last);
-        };
-        for (int it = 0; it < nit; ++it) {
-            auto &ri = RA_;  // this iteration's reads of the launch arguments
-            const int k = ri.k0 + it - sf;  // k0 - 1 on the select_first iteration
-            const int ts = ri.ts0 + (k - ri.k0);
-            const bool first_sel = it < sf;
-            if (!first_sel && !(ASG_ROLLOUT_XSKIP & 256))
-                rollout_transition<TAB, SQ>(RA_, e, k, ts, key, s_scl, s_cnt, s_act, s_prev, s_ret);
-            const int kk = k + 1;
-            if (has_agent(ri, it)) {
-                const bool next_agent = has_agent(ri, it + 1);
-                for (int sub = 0; sub < ntile; ++sub) {
-                    // the next agent tile: this pass's next tile (same h_t source), else tile 0
-                    // of the next pass (h_t = the h' this pass writes)
-                    HNext nx{nullptr, kHid, 0, 0};
-                    if (sub + 1 < ntile) nx = HNext{pass == 0 ? ri.Hin : ri.Hout, pass == 0 ? ri.hs : kHid,
-                                                    (int64_t)(16 * kH2NT) * (sub + 1), 1};
-                    else if (next_agent) nx = HNext{ri.Hout, kHid, 0, 1};
-                    // the reset row (select_first) is stored here when the reset runs in this launch
-                    rollout_tile<RNN, W2L, GEN, TAB, QOUT, true, SQ>(RA_, e, sub, kk, ts + 1, !first_sel || ri.reset, !first_sel, pass,
-                                                      key, s_scl, s_act, s_h2, sw, hN, hpf, nx);
-                    hpf = nx.mode != 0;
-                }
-                ++pass;
-            } else {
-                for (int sub = 0; sub < ntile; ++sub)
-                    rollout_tile<RNN, W2L, GEN, TAB, QOUT, false, SQ>(RA_, e, sub, kk, ts + 1, true, true, 0, key, s_scl, s_act, s_h2,
-                                                       sw, hN, false, HNext{nullptr, kHid, 0, 0});
-            }
-#undef RA_
-            wave_lds_fence();
-        }
-        for (int i = lane; i < n; i += 64) ra.prev[e * n + i] = s_prev[i];
-        if (lane == 0) ra.returns[e] = *s_ret;
-        wave_lds_fence();  // the next env reuses the scratch
-    }
-}
-
-// The rollout kernel's instances, one launcher per translation unit (the instances dominate
-// the build: asg_h2.hip holds the Philox epsilon-greedy ones, asg_rollout_tab.hip the table
-// modes', asg_rollout_q.hip the Q-output ones of both benefit sources).
-struct RolloutLaunch {
-    unsigned grid;
-    size_t lds;
-    bool rnn, w2l, gen;
-    bool sq64;  // n = m = 64 (W2 in LDS, no ragged tiles): the compile-time-shape instances
-};
-// TAB: 0 = Philox bumps, 1 = the dense float32 table (injected sat_prox_mat), 2 = the compact
-// one (MT19937 draws: RolloutArgs::tmask)
-template <int TAB, bool QOUT>
-static hipError_t launch_rollout_inst(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s) {
-#define LR_(RNN, W2L, GEN, SQ) \
-    hipLaunchKernelGGL((rollout_kernel<RNN, W2L, GEN, TAB, QOUT, SQ>), dim3(lc.grid), dim3(64 * kH2Waves), lc.lds, s, ra)
-#define LR2_(RNN)                                                                \
-    do {                                                                         \
-        if (lc.sq64) {                                                           \
-            LR_(RNN, true, false, 64);                                           \
-        } else if (lc.w2l) {                                                     \
-            if (lc.gen) LR_(RNN, true, true, 0); else LR_(RNN, true, false, 0);   \
-        } else {                                                                 \
-            if (lc.gen) LR_(RNN, false, true, 0); else LR_(RNN, false, false, 0); \
-        }                                                                        \
-    } while (0)
-    if (lc.rnn) LR2_(true); else LR2_(false);
-#undef LR2_
-#undef LR_
-    return hipGetLastError();
-}
-hipError_t launch_rollout_tab(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s);
-hipError_t launch_rollout_q(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s);
-
-#if ASG_H2_TU == 1
-hipError_t launch_rollout_tab(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s) {
-    return ra.tmask ? launch_rollout_inst<2, false>(ra, lc, s) : launch_rollout_inst<1, false>(ra, lc, s);
-}
-#elif ASG_H2_TU == 2
-hipError_t launch_rollout_q(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s) {
-    if (!ra.table32) return launch_rollout_inst<0, true>(ra, lc, s);
-    return ra.tmask ? launch_rollout_inst<2, true>(ra, lc, s) : launch_rollout_inst<1, true>(ra, lc, s);
-}
-#else
 // shapes the rollout kernel takes: the split-f16 agent with the mock env's obs layout
 // (K = m (L + 1), one-hot prefix geometry), n, m <= 256
 bool rollout_shape_ok(int n, int m, int L, int K) {
@@ -2005,14 +279,12 @@ hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, in
     lc.rnn = rnn;
     lc.w2l = plan.w2l;
     lc.gen = st.m % 32 != 0 || st.n % 32 != 0;
-    lc.sq64 = st.n == 64 && st.m == 64 && plan.w2l && ASG_ROLLOUT_SQ64 && (!ASG_SQ64_L3 || st.L == 3) &&
-              (!tab || ASG_ROLLOUT_SQ64_TAB);
-    // the L2 fc1 slice read first, before the tile's stores (rollout_tile's l2first)
-    if (lc.sq64 && ASG_ROLLOUT_L2FIRST && plan.l2_slices >= 1) ra.w1_off = 1;
+    lc.sq64 = st.n == 64 && st.m == 64 && plan.w2l;
+    // the L2 fc1 slice read first, before the tile's stores (rollout_tile's w1_off)
+    if (lc.sq64 && plan.l2_slices >= 1) ra.w1_off = 1;
     if (Q) return launch_rollout_q(ra, lc, s);
     if (tab) return launch_rollout_tab(ra, lc, s);
     return launch_rollout_inst<0, false>(ra, lc, s);
 }
-#endif  // ASG_H2_TU
 
 }  // namespace asg

@@ -1,4 +1,14 @@
 // asg_rollout_q.hip -- the rollout kernel instances that write the agent's Q rows instead of
-// selecting (asg_step_forward, both benefit sources): asg_h2.hip compiled for launch_rollout_q only.
-#define ASG_H2_TU 2
-#include "asg_h2.hip"
+// selecting (asg_step_forward / asg_reset_forward, both benefit sources).
+#include "rollout_tile.h"
+
+#pragma clang fp contract(fast)
+
+namespace asg {
+
+hipError_t launch_rollout_q(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s) {
+    if (!ra.table32) return launch_rollout_inst<0, true>(ra, lc, s);
+    return ra.tmask ? launch_rollout_inst<2, true>(ra, lc, s) : launch_rollout_inst<1, true>(ra, lc, s);
+}
+
+}  // namespace asg

@@ -104,8 +104,8 @@ def test_agent_pack_layout_without_gpu(L):
     """Host-only sizing of the packed agent buffer.  n_out <= 256 (the split-f16 path, GRU or
     Linear, any K): W1^T of the one-hot prefix (prefix geometry), then the section -- header,
     W1 planes over the block-padded inputs, the recurrent planes (GRU: W_ih + W_hh, 6 gates;
-    Linear: 1), W2 planes.  n_out > 256: f32 W1 fragments, the GRU as three bf16 planes, f32 W2,
-    W1^T of the one-hot prefix when n_out % 16 == 0, n_out < K and K % 32 == 0."""
+    Linear: 1), W2 planes.  n_out > 256: f32 W1 fragments, the GRU as three bf16 planes, f32 W2
+    (no one-hot prefix section, also at n_out % 16 == 0, n_out < K and K % 32 == 0)."""
     mode = L.asg_rnn_agent_mfma_mode()
     assert mode & 1 == 1
     gru = 3 * 4 * 2 * 3 * 64 if mode & 1 else 4 * 12 * 64
@@ -117,12 +117,11 @@ def test_agent_pack_layout_without_gpu(L):
             ((m + 15) // 16) * 256
         assert L.asg_rnn_agent_packed_size(K, 64, m, rnn) == 16 * size, (K, m, rnn)
         assert L.asg_rnn_agent_mode(K, 64, m, rnn) == 4
-    for K, m, rnn in [(490, 450, 1), (576, 300, 0)]:
+    for K, m, rnn in [(490, 450, 1), (576, 300, 0), (544, 272, 1), (640, 320, 0)]:
         wr = 2 * gru if rnn else 4 * 4 * 64
         w1 = ((K + 15) // 16) * 4 * 64
         w2 = 4 * ((m + 15) // 16) * 64
-        P = m if (m % 16 == 0 and m < K and K % 32 == 0) else 0
-        assert L.asg_rnn_agent_packed_size(K, 64, m, rnn) == 16 * (w1 + wr + w2 + 16 * P + w1x3(K)), (K, m, rnn)
+        assert L.asg_rnn_agent_packed_size(K, 64, m, rnn) == 16 * (w1 + wr + w2 + w1x3(K)), (K, m, rnn)
         assert L.asg_rnn_agent_mode(K, 64, m, rnn) == mode
     assert L.asg_rnn_agent_packed_size(256, 32, 64, 1) < 0  # hidden must be 64
 

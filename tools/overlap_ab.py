@@ -7,8 +7,7 @@ serial: one env handle of E envs, per step fused agent + epsilon-greedy selectio
 halves: two handles of E/2 envs (global env indices [0, E/2) and [E/2, E)) over the two
         halves of ONE time-major EpisodeBatch, each with its own MAC hidden state and its
         own stream; the selection of one half can run while the other half's env step
-        kernel streams its HBM writes.  Co-residency needs the persistent agent kernel's
-        registers to leave room for a step wave (build with -DASG_AGENT_NUM_VGPR=224).
+        kernel streams its HBM writes.
 Prints one JSON line with ms/step and env-steps/s.
 """
 import argparse
