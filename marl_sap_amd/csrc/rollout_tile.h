@@ -240,6 +240,54 @@ __device__ __forceinline__ void st_i64x2(int64_t *p, long long a, long long b) {
     *reinterpret_cast<i64x2v *>(p) = i64x2v{a, b};
 }
 
+// The rows of a 32-agent tile that depend on nothing but the tile's actions, n = m = 64 (the
+// SQ64 instances): obs block 0 = onehot(a), actions_onehot (oh, NULL = none) and avail = 1 (av,
+// NULL = none), every store instruction 1 KiB of whole lines instead of the MFMA operand layout
+// of the generated blocks (16 rows x 64 B per instruction for block 0, 16-B pieces at a 32-B
+// stride for the int64 one-hot).  Any lane can read any row's action from the wave's LDS:
+//   actions_onehot: the tile's 32 rows x 512 B are one 16 KiB span; instruction i writes rows
+//     2 i and 2 i + 1 whole: lane l takes row 2 i + (l >> 5), columns 2 (l & 31) and the next
+//   obs block 0: instruction i writes rows 4 i .. 4 i + 3, 256 B each: lane l takes row
+//     4 i + (l >> 4), columns 4 (l & 15) .. + 3
+//   avail: the tile's 2 KiB, two instructions
+// ob / oh / av: the tile's first row (wave-uniform), K the obs row length; sa: the tile's
+// actions; have_act false (the reset row): block 0 is zeros.  The lane index is laundered
+// here and every address is a uniform base plus a 32-bit lane offset: no per-lane 64-bit
+// pointer to keep across tiles.
+__device__ __forceinline__ void tile_action_rows64(float *ob, int64_t *oh, uint8_t *av, int K, const uint16_t *sa,
+                                                   bool have_act) {
+    constexpr int RT = 16 * kH2NT, M = 64;
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    {
+        const int rl = lane >> 4, c0 = 4 * (lane & 15);
+        const uint32_t lo = (uint32_t)(rl * K + c0);
+        // no action: a column no action reaches (one select per tile; the LDS reads stay
+        // unconditional, a branch per instruction would wait for each read on its own)
+        const int cc = have_act ? c0 : 0x10000;
+#pragma unroll
+        for (int i = 0; i < RT / 4; ++i) {
+            const int d = (int)sa[4 * i + rl] - cc;
+            st_f4(ob + (uint32_t)(4 * i * K) + lo, d == 0, d == 1, d == 2, d == 3);
+        }
+    }
+    if (oh) {
+        const int rl = lane >> 5, c0 = 2 * (lane & 31);
+        const uint32_t lo = (uint32_t)(2 * lane);
+#pragma unroll
+        for (int i = 0; i < RT / 2; ++i) {
+            const int d = (int)sa[2 * i + rl] - c0;
+            st_i64x2(oh + 2 * M * i + lo, d == 0, d == 1);
+        }
+    }
+    if (av) {
+        const uint32_t lo = (uint32_t)(16 * lane);
+#pragma unroll
+        for (int i = 0; i < RT * M / 1024; ++i)
+            *reinterpret_cast<u32x4v *>(av + 1024 * i + lo) = u32x4v{0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
+    }
+}
+
 // One 32-agent tile of env e for observation row kk (batch row tsr): write the row (STORES:
 // one-hot block and actions_onehot of the transition before it, avail, lookahead blocks,
 // beta) and, AGENT, run fc1 on the generated blocks plus the recurrent layer, fc2 and the
@@ -383,7 +431,11 @@ __device__ __forceinline__ void rollout_tile(RA &ra, int64_t e, int sub, int kk,
         // obs block 0 = onehot(a) (row kk), actions_onehot (row kk - 1), avail = 1 (row kk)
         // actions_onehot of the transition before the row (none before the reset row)
         int64_t *oh_r = (ra.onehot && have_act) ? ra.onehot + ((int64_t)(tss - 1) * ra.E * n + sro) * m : nullptr;
-        for (int u = 0; u < Ub; ++u)
+        uint8_t *ab = ra.avail ? ra.avail + ((int64_t)tss * ra.E * n + sro + row0) * m : nullptr;
+        // n = m = 64: the three as whole-line instructions; else in the generated blocks' layout
+        if constexpr (SQ == 64)
+            tile_action_rows64(obs_r + row0 * K, oh_r ? oh_r + row0 * m : nullptr, ab, K, s_act + RT * sub, have_act);
+        for (int u = 0; u < (SQ == 64 ? 0 : Ub); ++u)
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -405,14 +457,15 @@ __device__ __forceinline__ void rollout_tile(RA &ra, int64_t e, int sub, int kk,
                             }
                     }
                 }
-        if (ra.avail) {
-            uint8_t *ab = ra.avail + ((int64_t)tss * ra.E * n + sro + row0) * m;
+        if (SQ != 64 && ab) {
             const int nrow = GEN ? min(RT, n - RT * sub) : RT;
             int off0 = (GEN ? 1 : 16) * lane;
             asm volatile("" : "+v"(off0));  // not hoisted: a per-lane 64-bit address kept across loops spilled
             if (!GEN) {
-                for (int off = off0; off < RT * m; off += 64 * 16)
-                    *reinterpret_cast<uint4 *>(ab + off) = make_uint4(0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u);
+                // RT m = 1 KiB x Ub: a uniform trip count, 16 B per lane and whole lines per instruction
+                for (int i = 0; i < Ub; ++i)
+                    *reinterpret_cast<u32x4v *>(ab + 1024 * i + (uint32_t)off0) =
+                        u32x4v{0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
             } else {
                 for (int off = off0; off < nrow * m; off += 64) ab[off] = 1;
             }

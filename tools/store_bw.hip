@@ -5,6 +5,7 @@
 //   rows16 : each instruction writes 16 rows x 64 B (lane (r, q): row r, bytes 16 q .. of the
 //            row's 64-B piece) -- the agent-tile obs stores (rows 1 KiB apart), the piece
 //            advancing with the next instruction
+//   oh16 / dw16 / rows4 : the tile's action-only rows, before and after (at their kernels below)
 //   nt     : `lines` with nontemporal stores
 //   reuse  : `lines` over a 256 MiB buffer rewritten `passes` times in the launch -- the REDA Q
 //            buffer's pattern (asg_step_forward rewrites the same 256 MiB every step): the
@@ -51,6 +52,63 @@ __global__ void __launch_bounds__(256) st_rows16(f32x4 *p, size_t n4, int passes
         }
 }
 
+// the rollout tile's action-only rows (actions_onehot, avail_actions, obs block 0), as the MFMA
+// operand layout issued them and as whole-line instructions issue block 0:
+// oh16: one wave owns 16 rows of 512 B (an int64 one-hot row of 64 tasks); the instruction pair
+// k writes bytes 128 k .. 128 k + 127 of each row: lane (r, q) -> row r, 16 B at 128 k + 32 q
+// with the first instruction and the 16 B after them with the second (16-B pieces at a 32-B
+// stride: each instruction covers half of every 64-B piece it touches)
+__global__ void __launch_bounds__(256) st_oh16(f32x4 *p, size_t n4, int passes) {
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const size_t nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+    const size_t tiles = n4 / (16 * 32);  // 16 rows x 32 f32x4 per tile
+    const f32x4 v = {1.f, 2.f, 3.f, (float)lane};
+    for (int it = 0; it < passes; ++it)
+        for (size_t t = wave; t < tiles; t += nwaves) {
+            f32x4 *row = p + t * 16 * 32 + (size_t)r * 32;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                row[8 * k + 2 * q] = v;
+                row[8 * k + 2 * q + 1] = v;
+            }
+        }
+}
+
+// dw16: each 1 KiB is written by four instructions of 4 B per lane at a 16-B stride (lane l,
+// instruction i: the dword at 16 l + 4 i); the index is laundered per store, or the compiler
+// merges the four into one 16-B store
+__global__ void __launch_bounds__(256) st_dw16(f32x4 *p, size_t n4, int passes) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (int it = 0; it < passes; ++it)
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                size_t w = 4 * i + d;
+                asm volatile("" : "+v"(w));
+                reinterpret_cast<float *>(p)[w] = (float)d;
+            }
+        }
+}
+
+// rows4: the rows16 tile (16 rows of 1 KiB), each instruction writing 4 rows x 256 B: lane l ->
+// row 4 i + (l >> 4), 16 B at 256 k + 16 (l & 15)
+__global__ void __launch_bounds__(256) st_rows4(f32x4 *p, size_t n4, int passes) {
+    const int lane = threadIdx.x & 63, r = lane >> 4, c = lane & 15;
+    const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const size_t nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+    const size_t tiles = n4 / (16 * 64);
+    const f32x4 v = {1.f, 2.f, 3.f, (float)lane};
+    for (int it = 0; it < passes; ++it)
+        for (size_t t = wave; t < tiles; t += nwaves) {
+            f32x4 *row = p + t * 16 * 64 + (size_t)r * 64 + c;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) row[(4 * i) * 64 + 16 * k] = v;
+        }
+}
+
 int main(int argc, char **argv) {
     const double gib = argc > 1 ? atof(argv[1]) : 32.0;
     const size_t tile = 16 * 64 * 16;
@@ -74,6 +132,9 @@ int main(int argc, char **argv) {
     } shapes[] = {{"lines", st_lines, bytes, 1},
                   {"rows16", st_rows16, bytes, 1},
                   {"nt", st_lines_nt, bytes, 1},
+                  {"oh16", st_oh16, bytes, 1},
+                  {"dw16", st_dw16, bytes, 1},
+                  {"rows4", st_rows4, bytes, 1},
                   {"reuse", st_lines, reuse_bytes, (int)(bytes / reuse_bytes)}};
     for (int occ : {2, 4, 8}) {
         const unsigned grid = (unsigned)(cus * occ);
