@@ -40,6 +40,10 @@
  *   asg_rnn_agent_unroll       the learner's loop of BasicMAC.forward over the T + 1 rows of a
  *                              sampled batch (learners/sap_q_learner.py:69-84) in one launch;
  *                              asg_rnn_agent_unroll_backward = autograd's walk back through it
+ *   asg_mlp_agent_unroll       the same loop for the Linear agent (use_rnn: False, the agent of
+ *                              mock_constellation_reda.yaml / mock_constellation_iql.yaml), as
+ *                              learners/q_learner.py:67-85 and sap_q_learner.py:69-84 run it;
+ *                              asg_mlp_agent_unroll_backward = autograd's way back through it
  *   asg_get_returns            the runners' episode_return accumulation
  *                              (episode_runner.py:84, parallel_runner.py:173-176)
  *   asg_filtered_*             FilteredSAPActionSelector / FilteredEpsGrSAPTestActionSelector
@@ -356,6 +360,39 @@ int asg_rnn_agent_unroll_backward(const float *dh_q, const float *dh_last, const
                                   const float *h_all, const float *h0, int64_t h_stride,
                                   const float *W_ih, const float *W_hh, int T1, int64_t R, int hidden,
                                   int n_out, int use_rnn, float *dgi, float *dgh_n, float *dx1, float *dh0,
+                                  void *hip_stream);
+
+/* ---- the Linear agent over a whole batch (use_rnn: False; the learners' unrolls) -----------
+ * asg_mlp_agent_unroll: RNNAgent.forward with the Linear middle layer on every (t, env, agent)
+ * row of a batch in one launch:
+ *     x1 = relu(W1 x + b1);  h = relu(W_r x1 + b_r);  q = W2 h + b2
+ * The agent has no recurrence, so the grid covers the flattened N = T1 * R rows (R = B * n;
+ * flattened row t * R + env * n + agent, the order of the outputs); a 16-row tile may straddle a
+ * time boundary.  x: element strides x_strides = {t, env, agent}, K contiguous, as
+ * asg_rnn_agent_unroll takes it (a batch-major ReplayBuffer sample and the time-major runner
+ * batch both fit, with no copy; float4 loads when K % 4 == 0 and x and its strides are 16-B
+ * aligned).  Weights in the torch layouts, contiguous: W1 [64][K], W_r [64][64], W2 [n_out][64],
+ * b1 [64], b_r [64], b2 [n_out].  Outputs, contiguous: q [T1][R][n_out], h_all [T1][R][64] and,
+ * when x1_save is not NULL, x1_save [T1][R][64] = relu(fc1), for the backward pass.  Exact f32
+ * MFMA products in a fixed order, no atomics: the same inputs give the same bits.
+ * ASG_E_INVALID_ARG before any device call when hidden != 64, n_out outside 1..512, T1 < 1,
+ * B * n < 1, K < 1, a required pointer is NULL or a pointer is misaligned. */
+int asg_mlp_agent_unroll(const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
+                         const float *W1, const float *W_r, const float *W2, const float *b1,
+                         const float *b_r, const float *b2, int hidden, int n_out, float *q,
+                         float *h_all, float *x1_save, void *hip_stream);
+/* Backpropagation through the two ReLUs and the middle layer of that pass, over the N = T1 * R
+ * flattened rows.  dh_q [N][64] is the gradient reaching each h through fc2 (dQ @ W2), with
+ * any gradient on the returned last hidden state already added into its last R rows; h_all
+ * and x1_save as asg_mlp_agent_unroll wrote them.
+ *     dh = dh_q (h_all > 0);  dx1 = (dh @ W_r) (x1_save > 0)
+ * Outputs: dh [N][64] and dx1 [N][64].  Exact f32 MFMA products in a fixed order, no atomics.
+ * The parameter gradients are GEMMs over the N rows (dW2 = dQ^T h_all, dW_r = dh^T x1,
+ * dW1 = dx1^T x, the bias gradients the column sums) left to the caller.
+ * ASG_E_INVALID_ARG before any device call when hidden != 64, N < 1, a pointer is NULL or
+ * misaligned (16 B). */
+int asg_mlp_agent_unroll_backward(const float *dh_q, const float *h_all, const float *x1_save,
+                                  const float *W_r, int64_t N, int hidden, float *dh, float *dx1,
                                   void *hip_stream);
 
 /* ---- filtered selectors (the real-env algorithms' action_selector) -------------------------

@@ -45,7 +45,8 @@ EXPORTS = ["asg_abi_version", "asg_last_error", "asg_create", "asg_destroy", "as
            "asg_rollout_l2_slices", "asg_reset_rollout", "asg_sap_select_into", "asg_step_forward",
            "asg_sap_noise", "asg_random_rollout", "asg_sap_select_warm", "asg_bids_select",
            "asg_reset_forward", "asg_step_ex", "asg_step_forward_ex", "asg_bids_select_count",
-           "asg_rnn_agent_unroll", "asg_rnn_agent_unroll_backward"]
+           "asg_rnn_agent_unroll", "asg_rnn_agent_unroll_backward", "asg_mlp_agent_unroll",
+           "asg_mlp_agent_unroll_backward"]
 
 
 class AsgField(ctypes.Structure):
@@ -140,6 +141,9 @@ def lib():
             L.asg_rnn_agent_unroll.argtypes = [vp, i64p, i32, i64, i32, i32, vp, i64] + [vp] * 8 + [i32, i32, i32,
                                                                                                  vp, vp, vp, vp]
             L.asg_rnn_agent_unroll_backward.argtypes = [vp] * 5 + [i64, vp, vp, i32, i64, i32, i32, i32] + [vp] * 5
+        if hasattr(L, "asg_mlp_agent_unroll"):
+            L.asg_mlp_agent_unroll.argtypes = [vp, i64p, i32, i64, i32, i32] + [vp] * 6 + [i32, i32, vp, vp, vp, vp]
+            L.asg_mlp_agent_unroll_backward.argtypes = [vp] * 4 + [i64, i32, vp, vp, vp]
         L.asg_real_create.argtypes = [ctypes.POINTER(AsgRealConfig), i32, vp, ctypes.POINTER(vp)]
         L.asg_real_destroy.argtypes = [vp]
         L.asg_real_destroy.restype = None

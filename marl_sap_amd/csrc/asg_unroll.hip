@@ -22,7 +22,7 @@
 // so two runs give identical bits.  The weights are read in their torch layouts (no packed
 // copy to keep in step with the optimiser): W_ih and W_hh (48 KiB each) are staged in LDS
 // once per workgroup -- row-padded forward, transposed backward -- W1 and W2 come through L2.
-#include "asg_agent_common.h"
+#include "unroll_common.h"
 
 namespace asg {
 namespace {
@@ -35,19 +35,6 @@ constexpr int kFc1G = 4;           // fc1 k-chunks (of 16 inputs) per register b
 constexpr size_t kFwdLds = 2 * (size_t)kG * kWS * sizeof(float);     // 104,448 B
 constexpr size_t kBwdLds = 2 * (size_t)kHid * kWTS * sizeof(float);  // 100,352 B
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
-// elements k .. k + 3 of a K-long row; vec: K % 4 == 0 and the row is 16-B aligned
-__device__ __forceinline__ f32x4 ldk(const float *row, int k, int K, bool vec) {
-    if (vec) return k < K ? ld4(row + k) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = k + e < K ? row[k + e] : 0.f;
-    return v;
-}
 __device__ __forceinline__ float sigmoid_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct FwdArgs {
@@ -334,15 +321,6 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_bwd_kernel(BwdArgs a) {
     }
 }
 
-int fail(const char *msg) {
-    set_last_error(msg);
-    return ASG_E_INVALID_ARG;
-}
-int hip_fail(hipError_t e, const char *what) {
-    set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-    return ASG_E_HIP;
-}
-bool al(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 // the shape both entries take: the GRU agent at hidden 64
 const char *shape_error(int T1, int64_t R, int hidden, int n_out, int use_rnn) {
     if (hidden != 64) return "hidden must be 64";

@@ -1,9 +1,12 @@
-"""Learners on the rollout path's kernels: the SAP Q-learner (REDA's training step) with the
-agent unrolled in one launch each way, and the batched LSA targets it uses (SURVEY §8(f)
-row 1).  Mixers, critics and the reference's other learners are not ported."""
+"""Learners on the rollout path's kernels: the SAP Q-learner (REDA's training step) and the
+Q-learner (IQL's: per-agent max targets), both with the agent unrolled in one launch each way
+(the GRU agent always, the Linear agent with fused_linear_unroll), and the batched LSA targets
+the SAP learner uses.  Mixers, critics and the reference's other learners
+are not ported."""
+from .q_learner import QLearner
 from .sap_q_learner import SAPQLearner
 from .sap_targets import sap_target_max_qvals
 
-REGISTRY = {"sap_q_learner": SAPQLearner}
+REGISTRY = {"sap_q_learner": SAPQLearner, "q_learner": QLearner}
 
-__all__ = ["REGISTRY", "SAPQLearner", "sap_target_max_qvals"]
+__all__ = ["REGISTRY", "QLearner", "SAPQLearner", "sap_target_max_qvals"]

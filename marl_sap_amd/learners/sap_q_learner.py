@@ -29,8 +29,8 @@ class SAPQLearner:
         self.mac = mac
         self.logger = logger
         if getattr(args, "mixer", None) is not None:
-            raise ValueError("Mixer {} is not supported: SAPQLearner is ported for mixer = None only"
-                             .format(args.mixer))
+            raise ValueError("Mixer {} is not supported: {} is ported for mixer = None only"
+                             .format(args.mixer, type(self).__name__))
         self.mixer = None
         self.params = list(mac.parameters())
         self.last_target_update_episode = 0
@@ -73,10 +73,7 @@ class SAPQLearner:
         # target-network Q-values (the first row is not needed for targets)
         with torch.no_grad():
             target_mac_out = self.target_mac.forward_sequence(batch)[:, 1:]
-            # unavailable actions at -9999, then the SAP maximum: the assignment of the target
-            # Q (or, double_q, of the live Q) per (episode, t), and the target Q it picks
-            target_max_qvals = sap_target_max_qvals(target_mac_out, avail_actions, mac_out,
-                                                    double_q=bool(self.args.double_q), mask_value=-9999.0)
+            target_max_qvals = self._target_max_qvals(target_mac_out, avail_actions, mac_out)
 
             if getattr(self.args, "standardise_returns", False):
                 target_max_qvals = target_max_qvals * torch.sqrt(self.ret_ms.var) + self.ret_ms.mean
@@ -121,6 +118,14 @@ class SAPQLearner:
             self.logger.log_stat("avg_num_conflicts", self.calc_conflicting_actions(actions), t_env)
             self.logger.log_stat("avg_beta", self.calc_raw_benefits(batch["beta"], actions), t_env)
         return loss.detach()
+
+    def _target_max_qvals(self, target_mac_out, avail_actions, mac_out):
+        """The target network's value of the next row, [B, T, n], from target_mac_out [B, T, n, m]
+        (rows 1..T), avail_actions and the live mac_out [B, T + 1, n, m]: unavailable actions at
+        -9999, then the SAP maximum -- the assignment of the target Q (or, double_q, of the live
+        Q) per (episode, t), and the target Q it picks."""
+        return sap_target_max_qvals(target_mac_out, avail_actions, mac_out, double_q=bool(self.args.double_q),
+                                    mask_value=-9999.0)
 
     def _clip_grads(self):
         return torch.nn.utils.clip_grad_norm_(self.params, self.args.grad_norm_clip)

@@ -130,13 +130,68 @@ def _unroll_launch(x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2, save):
     return q, h_all, sv
 
 
+class _MLPUnroll(torch.autograd.Function):
+    """asg_mlp_agent_unroll under autograd (the Linear agent): the forward kernel saves x1 and
+    h of every row, asg_mlp_agent_unroll_backward takes the gradient back through the two ReLUs
+    and the middle layer, and the parameter gradients are GEMMs over the T1 * R rows."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, Wr, br, W2, b2):
+        q, h_all, x1 = _mlp_launch(x, W1, b1, Wr, br, W2, b2, True)
+        ctx.save_for_backward(x, Wr, W2, h_all, x1)
+        B, T1, n, _ = x.shape
+        return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
+
+    @staticmethod
+    def backward(ctx, dq, dh_last):
+        x, Wr, W2, h_all, x1 = ctx.saved_tensors
+        B, T1, n, K = x.shape
+        R, H, n_out = B * n, Wr.shape[1], W2.shape[0]
+        N = T1 * R
+        dev = x.device
+        if dq is None:
+            dQ = torch.zeros((N, n_out), dtype=torch.float32, device=dev)
+        else:
+            dQ = dq.permute(1, 0, 2, 3).reshape(N, n_out).float().contiguous()
+        dh_q = dQ @ W2
+        if dh_last is not None:
+            dh_q[N - R:] += dh_last.reshape(R, H).float()
+        dh = torch.empty((N, H), dtype=torch.float32, device=dev)
+        dx1 = torch.empty((N, H), dtype=torch.float32, device=dev)
+        Wrc = Wr.detach().contiguous()
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().asg_mlp_agent_unroll_backward(
+                p(dh_q), p(h_all), p(x1), p(Wrc), N, H, p(dh), p(dx1), _lib.stream_ptr(dev)))
+        xf = x.permute(1, 0, 2, 3).reshape(N, K)
+        return (None, dx1.t() @ xf, dx1.sum(0), dh.t() @ x1.view(N, H), dh.sum(0), dQ.t() @ h_all.view(N, H),
+                dQ.sum(0))
+
+
+def _mlp_launch(x, W1, b1, Wr, br, W2, b2, save):
+    B, T1, n, K = x.shape
+    R, H, n_out = B * n, Wr.shape[1], W2.shape[0]
+    dev = x.device
+    q = torch.empty((T1, R, n_out), dtype=torch.float32, device=dev)
+    h_all = torch.empty((T1, R, H), dtype=torch.float32, device=dev)
+    x1 = torch.empty((T1, R, H), dtype=torch.float32, device=dev) if save else None
+    ws = [t.detach().contiguous() for t in (W1, Wr, W2, b1, br, b2)]
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().asg_mlp_agent_unroll(
+            p(x), _lib.i64arr([x.stride(1), x.stride(0), x.stride(2)]), T1, B, n, K, *[p(w) for w in ws], H, n_out,
+            p(q), p(h_all), p(x1), _lib.stream_ptr(dev)))
+    return q, h_all, x1
+
+
 class RNNFusedAgent(RNNAgent):
     """RNNAgent with the same parameters / state_dict, whose inference forward (no autograd:
     the rollout's action selection) is one fused HIP kernel (asg_rnn_agent_forward: f32
     MFMA, fc1 + GRUCell + fc2 with every intermediate in registers; hidden 64, any input
     size, n_out = m up to 512 -- the real envs' m = 450 included).  With autograd enabled
     (learner training) it is the plain PyTorch module, so gradients are unchanged.  unroll()
-    runs a whole sequence, and its backward pass, in one launch each (asg_unroll.hip)."""
+    runs a whole sequence, and its backward pass, in one launch each (asg_unroll.hip; the
+    Linear agent with args.fused_linear_unroll: asg_unroll_mlp.hip)."""
 
     def __init__(self, input_shape, args, n_out=None):
         super().__init__(input_shape, args, n_out)
@@ -227,11 +282,18 @@ class RNNFusedAgent(RNNAgent):
         """x [B, T1, n, K] (any batch / time / agent strides, contiguous K) -> (q [B, T1, n,
         n_out], h_last [B * n, hidden]).  The GRU agent on the GPU runs the whole sequence
         in one launch (asg_rnn_agent_unroll; under autograd with its one-launch backward,
-        asg_rnn_agent_unroll_backward, differentiable in the eight parameter tensors and h0); the
-        Linear agent and CPU tensors loop the module over t, as does args.unfused_unroll = True
+        asg_rnn_agent_unroll_backward, differentiable in the eight parameter tensors and h0).  The
+        Linear agent on the GPU does the same with args.fused_linear_unroll = True
+        (asg_mlp_agent_unroll / asg_mlp_agent_unroll_backward over the flattened T1 * B * n rows,
+        differentiable in its six parameter tensors; it ignores h0, as forward does); without
+        that flag it loops the module over t, as do CPU tensors and args.unfused_unroll = True
         (the A/B switch of tools/bench_learner.py)."""
-        if not (self.args.use_rnn and x.is_cuda and x.dim() == 4) or getattr(self.args, "unfused_unroll", False):
+        if not (x.is_cuda and x.dim() == 4) or getattr(self.args, "unfused_unroll", False):
             return self._unroll_loop(x, h0)
+        if not self.args.use_rnn:
+            if not getattr(self.args, "fused_linear_unroll", False):
+                return self._unroll_loop(x, h0)
+            return self._unroll_linear(x)
         if x.dtype != torch.float32 or x.stride(-1) != 1:
             x = x.float().contiguous()
         x = x.detach()  # observations are data: no gradient flows into them
@@ -241,6 +303,17 @@ class RNNFusedAgent(RNNAgent):
         if torch.is_grad_enabled() and (any(w.requires_grad for w in ps) or (h0 is not None and h0.requires_grad)):
             return _GRUUnroll.apply(x, h0, *ps)
         q, h_all, _ = _unroll_launch(x, h0, *ps, False)
+        return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
+
+    def _unroll_linear(self, x):
+        if x.dtype != torch.float32 or x.stride(-1) != 1:
+            x = x.float().contiguous()
+        x = x.detach()  # observations are data: no gradient flows into them
+        B, T1, n, _ = x.shape
+        ps = (self.fc1.weight, self.fc1.bias, self.rnn.weight, self.rnn.bias, self.fc2.weight, self.fc2.bias)
+        if torch.is_grad_enabled() and any(w.requires_grad for w in ps):
+            return _MLPUnroll.apply(x, *ps)
+        q, h_all, _ = _mlp_launch(x, *ps, False)
         return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
 
     def _packed(self, K, device):
