@@ -272,14 +272,26 @@ hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, in
     ra.w1_off = 0;  // 1 with the SQ64 instances (below)
     ra.scratch_off = plan.scratch_off;
     const int ncu = stream_cus(s);
-    const int64_t wgs = (st.E + kH2Waves - 1) / kH2Waves;
     RolloutLaunch lc;
-    lc.grid = (unsigned)(wgs < ncu ? wgs : ncu);
     lc.lds = plan.bytes;
     lc.rnn = rnn;
     lc.w2l = plan.w2l;
     lc.gen = st.m % 32 != 0 || st.n % 32 != 0;
     lc.sq64 = st.n == 64 && st.m == 64 && plan.w2l;
+    // agent passes of the launch (the kernel's has_agent): with two or more, the SQ64 selecting
+    // instances keep the hidden state in registers between them (rollout_envs_pair); a single
+    // pass has nothing to keep and runs one wave per env
+    int passes = 0;
+    for (int it = 0, nit = steps + (select_first ? 1 : 0); it < nit; ++it) {
+        const int kk = k0 + it - (select_first ? 1 : 0) + 1;
+        passes += kk < st.T && (kk < ra.k1 || select_last);
+    }
+    lc.pair = lc.sq64 && !Q && passes >= 2;
+    // envs in flight per workgroup: one per wave, or one per wave pair, whose scratch is the
+    // pair's two wave slots of the plan above
+    const int per_wg = lc.pair ? kH2Waves / 2 : kH2Waves;
+    const int64_t wgs = (st.E + per_wg - 1) / per_wg;
+    lc.grid = (unsigned)(wgs < ncu ? wgs : ncu);
     // the L2 fc1 slice read first, before the tile's stores (rollout_tile's w1_off)
     if (lc.sq64 && plan.l2_slices >= 1) ra.w1_off = 1;
     if (Q) return launch_rollout_q(ra, lc, s);

@@ -174,7 +174,10 @@ constexpr int kH2SxInit = 11;                   // fc1 input scale of the first 
 // Timing-only switches (WRONG results; refused without -DASG_TIMING_EXPERIMENTS):
 // ASG_ROLLOUT_XSKIP bit 1: no batch row stores in the rollout tiles; bit 2: no one-hot W1
 // column gather (zeros); bit 4: fc1 slices that live in L2 read LDS slot 0 instead; bit 8:
-// h_t not loaded (constants); bit 16: h' not stored; bit 32: the tile's row stores go to a
+// h_t not loaded (constants); bit 16: h' not stored (the SQ64 wave-pair rollout instances keep h
+// in registers between a launch's passes: there bit 8 still replaces h_t by the constants in
+// every pass -- the carried h' is ignored -- but the load it no longer waits for happens once
+// per launch, and bit 16 drops the launch's one h' store); bit 32: the tile's row stores go to a
 // small region that stays in L2 (env e & 7, batch row 1): same instructions, no HBM writes;
 // bit 64: the tiles' bump parameters from a cheap hash instead of Philox (VALU); bit 256: no env
 // transition between the steps (rewards, returns, the transition's rows); bit 512: the return
@@ -234,16 +237,20 @@ __device__ __forceinline__ void h2_stage(const H2Args &a, u32x4v *s, int (&sw)[4
 // ALLAV: every task is available (the rollout wrote avail = 1 itself).  act_lds (rollout):
 // also receives each row's selected task (index lrow0 + row within the tile).
 struct NoTailHook {
-    __device__ void operator()() const {}
+    template <class H>
+    __device__ void operator()(const H &) const {}
 };
 
-// after_rec: called once the recurrent layer has consumed hB and stored h' (the rollout
-// issues the next agent tile's h_t loads there)
-template <int NT, bool RNN, bool SEL, bool W2L, bool ALLAV, bool GEN, class Hook = NoTailHook, class A>
+// after_rec(hp): called once the recurrent layer has consumed hB and stored h', with the h'
+// fragments (the layout hB came in; the rollout issues the next agent tile's h_t loads there,
+// or -- the SQ64 instances -- keeps hp as that tile's h_t).  HCOND: h' goes to Hout only when
+// store_h says so (the wave-pair rollout: the launch's last agent pass); false = always.
+template <int NT, bool RNN, bool SEL, bool W2L, bool ALLAV, bool GEN, bool HCOND = false, class Hook = NoTailHook,
+          class A>
 __device__ __forceinline__ void h2_tail(A &a, const u32x4v *Wl, const int (&sw)[4], int64_t row0,
                                         const int64_t (&rows)[NT], const bool (&ok)[NT], const float4 (&hB)[4][NT],
                                         const f32x4 (&xB)[4][NT], uint16_t *act_lds = nullptr, int lrow0 = 0,
-                                        const Hook &after_rec = Hook{}) {
+                                        const Hook &after_rec = Hook{}, bool store_h = true) {
     // lane-derived addresses are recomputed here, not hoisted out of the callers' step / env
     // loops (there they would be live across every tile and spill; their reloads would wait
     // behind the tile stores in the in-order vmcnt queue)
@@ -410,7 +417,7 @@ __device__ __forceinline__ void h2_tail(A &a, const u32x4v *Wl, const int (&sw)[
                 }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
-                if (ok[nt] && !(ALLAV && (ASG_ROLLOUT_XSKIP & 16)))
+                if (ok[nt] && !(ALLAV && (ASG_ROLLOUT_XSKIP & 16)) && (!HCOND || store_h))
                     *reinterpret_cast<float4 *>(a.Hout + rows[nt] * kHid + 16 * hb + 4 * q) =
                         make_float4(hp[hb][nt][0], hp[hb][nt][1], hp[hb][nt][2], hp[hb][nt][3]);
         }
@@ -441,14 +448,14 @@ __device__ __forceinline__ void h2_tail(A &a, const u32x4v *Wl, const int (&sw)[
             for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
                 for (int v = 0; v < 4; ++v) hp[hb][nt][v] = fmaxf(acc[nt][v] * un[nt], 0.f);
-                if (ok[nt])
+                if (ok[nt] && (!HCOND || store_h))
                     *reinterpret_cast<float4 *>(a.Hout + rows[nt] * kHid + 16 * hb + 4 * q) =
                         make_float4(hp[hb][nt][0], hp[hb][nt][1], hp[hb][nt][2], hp[hb][nt][3]);
             }
         }
     }
 
-    after_rec();
+    after_rec(hp);
     // ---- fc2 (+ selection state), per-row scale --------------------------------------------
     int S3[NT];
     u32x4v hq[2][NT][2];

@@ -23,7 +23,10 @@ namespace asg {
 // evaluates the Philox bumps of tasks 32 u + 16 c + 4 q + v), write it to the batch and feed
 // fc1 from registers: the agent never reads an observation back.  Selected tasks go to the
 // batch's actions row and to the LDS, where the next transition reads them.  The hidden
-// state lives in Hout between passes (Hin for the first).  Results are those of the separate
+// state lives in Hout between passes (Hin for the first) -- except in the n = m = 64 launches
+// with two or more agent passes, where a wave PAIR shares the env, each wave runs the same
+// 32-agent tile in every pass and keeps its h in registers (rollout_envs_pair: Hin read by the
+// first pass, Hout written by the last).  Results are those of the separate
 // launches: asg_reset / asg_step rows, and the agent kernel's actions and hidden state
 // (per-row scales make a row's result independent of its tile's other rows).
 // =====================================================================================
@@ -69,7 +72,7 @@ struct RolloutArgs {
     float epsilon;
     uint32_t sk0, sk1, counter;
     int *sel_err;
-    int64_t scratch_off;  // per-wave LDS scratch (u32x4v units)
+    int64_t scratch_off;  // per-wave LDS scratch (u32x4v units; a wave pair's = its two waves' slots)
     // bids_as_actions (asg_step_forward): the tasks of transition k0 are the handle's LSA
     // assignments of the bids row [E][n] instead of the batch's actions row
     const int *assign;
@@ -85,11 +88,11 @@ __device__ __forceinline__ KRolloutArgs &rollout_args(KRolloutArgs *p) {
     return *p;
 }
 
-__host__ __device__ inline int rollout_mp(int m) { return (m + 31) / 32 * 32; }
-__host__ __device__ inline int rollout_np(int n) { return (n + 31) / 32 * 32; }
+__host__ __device__ constexpr int rollout_mp(int m) { return (m + 31) / 32 * 32; }
+__host__ __device__ constexpr int rollout_np(int n) { return (n + 31) / 32 * 32; }
 // per wave: task-scale bits [4] u64 | the env's return f64 | collision counts [mp] int |
 // selected / previous tasks [np] u16 each
-__host__ __device__ inline int rollout_scratch_bytes(int n, int m) {
+__host__ __device__ constexpr int rollout_scratch_bytes(int n, int m) {
     return (40 + 4 * rollout_mp(m) + 4 * rollout_np(n) + 15) / 16 * 16;
 }
 
@@ -298,6 +301,8 @@ __device__ __forceinline__ void tile_action_rows64(float *ob, int64_t *oh, uint8
 // store of the tile: gfx9's vmcnt retires memory operations in order).  After the recurrent
 // layer the tile issues the NEXT agent tile's h_t loads into hN (nsrc: its source rows, row
 // nrow0 on, stride nhs; NULL source = zeros; nmode 0 = no next agent tile in this env).
+// With a wave pair per env (HKeep) hN instead takes this tile's h' in registers: hpf is true
+// from the launch's second pass on and nothing is loaded.
 // The compact same-seed table (RolloutArgs::tmask): the 4 tasks j0 .. j0 + 3 of a row (j0 % 4 == 0,
 // one mask word) are the set bits `nib` of the row's mask word at sh = j0 % 64, and their values
 // sit at consecutive compact indices from pos = the word's first index + the bumps below sh.  One
@@ -331,6 +336,12 @@ struct HNext {
     int64_t stride, row0;
     int mode;
 };
+// The SQ64 instances (wave pair per env, below) have no next-tile loads: a wave's next agent
+// tile is the same 32 agents one step later, so hN takes h' in registers after the recurrent
+// layer, and h' goes to Hout only when `store` says so (the launch's last agent pass).
+struct HKeep {
+    int store;
+};
 
 // With W2 in LDS and an fc1 slice in L2 (64 x 64: 1 of 6; the SQ64 instances), that slice is
 // the tile's first (w1_off = 1; as the last one its weights were read behind nearly all the
@@ -341,11 +352,14 @@ struct HNext {
 // spilled with 1 block, 51 with 2, 84 with 3; the dense instance: 36 / 19 / 36)
 constexpr int kTabPre = 2;
 constexpr int kTabPreCmp = 1;
-template <bool RNN, bool W2L, bool GEN, int TAB, bool QOUT, bool AGENT, int SQ, class RA>
+// s_act: the env's tasks the row is built from; s_actw: where the selection puts the row's own
+// (the same array with one wave per env; the other parity buffer with a wave pair per env).
+// nx: HNext (run-time shapes), HKeep (SQ64).
+template <bool RNN, bool W2L, bool GEN, int TAB, bool QOUT, bool AGENT, int SQ, class HX, class RA>
 __device__ __forceinline__ void rollout_tile(RA &ra, int64_t e, int sub, int kk, int tsr, bool stores,
                                              bool have_act, int pass, const EnvKey &key, const uint64_t *s_scl,
-                                             uint16_t *s_act, const u32x4v *Wl, const int (&sw)[4],
-                                             f32x4 (&hN)[4][kH2NT], bool hpf, HNext nx) {
+                                             const uint16_t *s_act, uint16_t *s_actw, const u32x4v *Wl,
+                                             const int (&sw)[4], f32x4 (&hN)[4][kH2NT], bool hpf, HX nx) {
     constexpr int NT = kH2NT;
     constexpr int RT = 16 * NT;  // rows per tile
     // opaque env / row indices and lane: addresses are formed here from them, not hoisted out
@@ -734,8 +748,20 @@ __device__ __forceinline__ void rollout_tile(RA &ra, int64_t e, int sub, int kk,
                 for (int v = 0; v < 4; ++v) xB[mt][nt][v] = fmaxf(acc[mt][nt][v] * un + bb[v], 0.f);
             }
         }
+        if constexpr (std::is_same<HX, HKeep>::value) {
+            // the wave's next agent tile is this one a step later: its h_t is this h'
+            auto keep = [&](const f32x4(&hp)[4][NT]) {
+                if (!RNN) return;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) hN[t][nt] = hp[t][nt];
+            };
+            h2_tail<NT, RNN, !QOUT, W2L, true, GEN, true>(a, Wl, sw, row0, rows, ok, hB, xB, s_actw, RT * sub, keep,
+                                                          nx.store != 0);
+        } else {
         // the next agent tile's h_t, issued once this tile's recurrent layer is done
-        auto prefetch = [&]() {
+        auto prefetch = [&](const auto &) {
             if (!RNN || nx.mode == 0) return;
             const int64_t nb = e * n + nx.row0;
 #pragma unroll
@@ -749,17 +775,17 @@ __device__ __forceinline__ void rollout_tile(RA &ra, int64_t e, int sub, int kk,
                                        : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
         };
-        h2_tail<NT, RNN, !QOUT, W2L, true, GEN>(a, Wl, sw, row0, rows, ok, hB, xB, s_act, RT * sub, prefetch);
+        h2_tail<NT, RNN, !QOUT, W2L, true, GEN>(a, Wl, sw, row0, rows, ok, hB, xB, s_actw, RT * sub, prefetch);
+        }
     }
 }
 
+// One wave per env, its tiles in turn: the run-time-shape instances, and the SQ64 launches with
+// a single agent pass (one launch per step, the Q-output schedule), where there is no hidden
+// state to keep between passes and the pair mapping's idle wave during the prologue and the
+// transition costs 2.8 % (profiles/ab_pairs_headline.txt).
 template <bool RNN, bool W2L, bool GEN, int TAB, bool QOUT, int SQ>
-__global__ void __launch_bounds__(64 * kH2Waves) __attribute__((amdgpu_waves_per_eu(kH2WavesPerSimd)))
-rollout_kernel(RolloutArgs ra) {
-    extern __shared__ u32x4v s_h2[];
-    int sw[4];
-    h2_stage<RNN, W2L>(rollout_h2args(ra), s_h2, sw);
-    __syncthreads();
+__device__ __forceinline__ void rollout_envs_wave(const RolloutArgs &ra, u32x4v *s_h2, const int (&sw)[4]) {
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n = rs_n<SQ>(ra), m = rs_m<SQ>(ra), mp = rollout_mp(m), np = rollout_np(n);
     char *scr = reinterpret_cast<char *>(s_h2 + ra.scratch_off) + wv * rollout_scratch_bytes(n, m);
@@ -861,14 +887,14 @@ rollout_kernel(RolloutArgs ra) {
                     // the reset row (select_first) is stored here when the reset runs in this launch
                     rollout_tile<RNN, W2L, GEN, TAB, QOUT, true, SQ>(rollout_args(kra), e, sub, kk, ts + 1,
                                                                      !first_sel || ri.reset, !first_sel, pass, key, s_scl,
-                                                                     s_act, s_h2, sw, hN, hpf, nx);
+                                                                     s_act, s_act, s_h2, sw, hN, hpf, nx);
                     hpf = nx.mode != 0;
                 }
                 ++pass;
             } else {
                 for (int sub = 0; sub < ntile; ++sub)
                     rollout_tile<RNN, W2L, GEN, TAB, QOUT, false, SQ>(rollout_args(kra), e, sub, kk, ts + 1, true, true, 0,
-                                                                      key, s_scl, s_act, s_h2, sw, hN, false,
+                                                                      key, s_scl, s_act, s_act, s_h2, sw, hN, false,
                                                                       HNext{nullptr, kHid, 0, 0});
             }
             wave_lds_fence();
@@ -879,6 +905,155 @@ rollout_kernel(RolloutArgs ra) {
     }
 }
 
+// The pair hand-off: every LDS write of the wave has landed (lgkmcnt), then the workgroup's
+// barrier.  No fence of workgroup scope: its release would also wait for every outstanding
+// global store (vmcnt(0): the tile's row stores; see wave_lds_fence).  Every wave of the
+// workgroup executes the same number of these (trip counts from launch-uniform values only).
+__device__ __forceinline__ void pair_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// pair scratch (bytes): task-scale bits, one u64 per wave at 32 sub | the env's return f64 at
+// 64 | collision counts [64] int at 80 | tasks [2][64] u16 at 336 (parity double buffer) |
+// previous tasks [64] u16 at 592.  It lives in the two waves' scratch slots of the LDS plan.
+constexpr int kPairScratchBytes = 720;
+static_assert(kPairScratchBytes <= 2 * rollout_scratch_bytes(64, 64), "pair scratch: two wave slots");
+
+// A wave pair per env, n = m = 64 (the SQ64 instances): waves 2 p and 2 p + 1 of the workgroup
+// are pair p, which takes envs 4 b + p, + 4 gridDim.x, ...; wave `sub` of the pair runs tile
+// `sub` of its env in every pass, so its next agent tile is the same 32 agents one step later
+// and the hidden state stays in its registers between passes (hN <- h' after the recurrent
+// layer): Hin is read by the launch's first agent pass, Hout written by its last.  One wave of
+// the pair (trw; on another SIMD from pair to pair) also runs the transitions, lane = agent, and
+// owns the env's return, counts and previous tasks.  The pair shares the tasks: the selection
+// of pass p writes buffer (p + 1) & 1, each wave its own 32 entries; the transition and the
+// tiles after it read all / their own 32 of that buffer once the step's barrier has passed.
+// A buffer is rewritten two barriers after it was filled and its readers lie between them, so
+// one barrier per step is enough.
+template <bool RNN, bool W2L, int TAB, bool QOUT>
+__device__ __forceinline__ void rollout_envs_pair(const RolloutArgs &ra, u32x4v *s_h2, const int (&sw)[4]) {
+    constexpr int SQ = 64, n = 64, m = 64;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int pr = wv >> 1, sub = wv & 1;
+    const bool trw = sub == (pr >> 1);
+    char *scr = reinterpret_cast<char *>(s_h2 + ra.scratch_off) + pr * (2 * rollout_scratch_bytes(n, m));
+    uint64_t *s_scl = reinterpret_cast<uint64_t *>(scr + 32 * sub);
+    double *s_ret = reinterpret_cast<double *>(scr + 64);
+    int *s_cnt = reinterpret_cast<int *>(scr + 80);
+    uint16_t *s_act2 = reinterpret_cast<uint16_t *>(scr + 336);
+    uint16_t *s_prev = reinterpret_cast<uint16_t *>(scr + 592);
+    constexpr int kPairs = kH2Waves / 2;
+    const int64_t GP = (int64_t)gridDim.x * kPairs;
+    // the loop bound is the workgroup's: a pair past E skips the work and takes the barriers
+    for (int64_t eb = (int64_t)blockIdx.x * kPairs; eb < ra.E; eb += GP) {
+        int64_t e = eb + pr;
+        asm volatile("" : "+s"(e));
+        const bool active = e < ra.E;
+        const EnvKey key = env_key(ra.seed, ra.env_base + e);
+        if (active) {
+            // task scales as bits (Philox mode): each wave its own copy
+            if (!TAB) {
+                const bool ten = philox_task_scale(key, ra.episode, lane) == 10.0f;
+                const uint64_t bits = __ballot(ten);
+                if (lane == 0) s_scl[0] = bits;
+            }
+            if (trw) {
+                if (!TAB && ra.reset) {
+                    // asg_reset: see rollout_envs_wave
+                    uint16_t *s_perm = reinterpret_cast<uint16_t *>(s_cnt), *s_jj = s_perm + m;
+                    s_perm[lane] = (uint16_t)lane;
+                    const u32x4 rr = philox4x32_10(u32x4{(uint32_t)lane, 0u, kCtrPerm, ra.episode}, key.k0, key.k1);
+                    s_jj[lane] = (uint16_t)(((uint64_t)rr.x * (uint64_t)(lane + 1)) >> 32);
+                    wave_lds_fence();
+                    if (lane == 0)
+                        for (int i = m - 1; i >= 1; --i) {
+                            const int jj = s_jj[i];
+                            const uint16_t t = s_perm[i];
+                            s_perm[i] = s_perm[jj];
+                            s_perm[jj] = t;
+                        }
+                    wave_lds_fence();
+                    const int p = (int)s_perm[lane];
+                    s_prev[lane] = (uint16_t)p;
+                    if (ra.prevb)
+                        ra.prevb[((int64_t)ra.ts0 * ra.E + e) * n + lane] = (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : p;
+                    if (lane == 0 && ra.filled) ra.filled[(int64_t)ra.ts0 * ra.E + e] = 1;
+                } else {
+                    const int p = ra.prev[e * n + lane];
+                    s_prev[lane] = (uint16_t)p;
+                    if (TAB && ra.reset && ra.prevb)
+                        ra.prevb[((int64_t)ra.ts0 * ra.E + e) * n + lane] = (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : p;
+                    if (TAB && ra.reset && lane == 0 && ra.filled) ra.filled[(int64_t)ra.ts0 * ra.E + e] = 1;
+                }
+                s_act2[lane] = 0;
+                if (lane == 0) *s_ret = ra.reset ? 0.0 : ra.returns[e];
+                if (!ra.select_first) rollout_actions_from_batch(ra, e, ra.ts0, s_act2);
+            }
+        }
+        wave_lds_fence();
+        pair_barrier();  // the batch's tasks (buffer 0) reach the other wave
+        KRolloutArgs *const kra = (KRolloutArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+        const int sf = ra.select_first ? 1 : 0;
+        const int nit = ra.k1 - ra.k0 + sf;
+        int pass = 0;
+        f32x4 hN[4][kH2NT];  // the wave's h_t rows: loaded by pass 0, h' of the pass before after it
+        auto has_agent = [&](auto &rr, int it) {
+            const int kk = rr.k0 + it - sf + 1;
+            return it < nit && kk < rr.T && (kk < rr.k1 || rr.select_last);
+        };
+        for (int it = 0; it < nit; ++it) {
+            auto &ri = rollout_args(kra);
+            const int k = ri.k0 + it - sf;
+            const int ts = ri.ts0 + (k - ri.k0);
+            const bool first_sel = it < sf;
+            const bool agent = has_agent(ri, it);
+            uint16_t *const sa = s_act2 + n * (pass & 1), *const saw = s_act2 + n * ((pass & 1) ^ 1);
+            if (active) {
+                if (trw && !first_sel && !(ASG_ROLLOUT_XSKIP & 256))
+                    rollout_transition<TAB, SQ>(rollout_args(kra), e, k, ts, key, s_scl, s_cnt, sa, s_prev, s_ret);
+                const int kk = k + 1;
+                if (agent) {
+                    // the launch's last agent pass stores h' (a scalar: as a bool it went through
+                    // a byte of scratch, reloaded behind the tile's stores)
+                    const int last = __builtin_amdgcn_readfirstlane(has_agent(ri, it + 1) ? 0 : 1);
+                    rollout_tile<RNN, W2L, false, TAB, QOUT, true, SQ>(rollout_args(kra), e, sub, kk, ts + 1,
+                                                                       !first_sel || ri.reset, !first_sel, pass, key, s_scl,
+                                                                       sa, saw, s_h2, sw, hN, pass > 0,
+                                                                       HKeep{last});
+                } else {
+                    rollout_tile<RNN, W2L, false, TAB, QOUT, false, SQ>(rollout_args(kra), e, sub, kk, ts + 1, true, true, 0,
+                                                                        key, s_scl, sa, saw, s_h2, sw, hN, false,
+                                                                        HKeep{0});
+                }
+            }
+            if (agent) ++pass;
+            wave_lds_fence();
+            pair_barrier();  // this pass's tasks reach the transition and the next tiles
+        }
+        if (active && trw) {
+            ra.prev[e * n + lane] = s_prev[lane];
+            if (lane == 0) ra.returns[e] = *s_ret;
+        }
+        wave_lds_fence();
+    }
+}
+
+template <bool RNN, bool W2L, bool GEN, int TAB, bool QOUT, int SQ, bool PAIR = false>
+__global__ void __launch_bounds__(64 * kH2Waves) __attribute__((amdgpu_waves_per_eu(kH2WavesPerSimd)))
+rollout_kernel(RolloutArgs ra) {
+    static_assert(!PAIR || (SQ == 64 && !GEN && !QOUT), "the wave-pair mapping: n = m = 64, selecting instances");
+    extern __shared__ u32x4v s_h2[];
+    int sw[4];
+    h2_stage<RNN, W2L>(rollout_h2args(ra), s_h2, sw);
+    __syncthreads();
+    if constexpr (PAIR) rollout_envs_pair<RNN, W2L, TAB, QOUT>(ra, s_h2, sw);
+    else rollout_envs_wave<RNN, W2L, GEN, TAB, QOUT, SQ>(ra, s_h2, sw);
+}
+
 // The rollout kernel's instances, one launcher per translation unit (the instances dominate
 // the build: asg_h2.hip holds the Philox epsilon-greedy ones, asg_rollout_tab.hip the table
 // modes', asg_rollout_q.hip the Q-output ones of both benefit sources).
@@ -887,22 +1062,27 @@ struct RolloutLaunch {
     size_t lds;
     bool rnn, w2l, gen;
     bool sq64;  // n = m = 64 (W2 in LDS, no ragged tiles): the compile-time-shape instances
+    bool pair;  // sq64 launches with two or more agent passes: a wave pair per env (rollout_envs_pair)
 };
 // TAB: 0 = Philox bumps, 1 = the dense float32 table (injected sat_prox_mat), 2 = the compact
 // one (MT19937 draws: RolloutArgs::tmask)
 template <int TAB, bool QOUT>
 static hipError_t launch_rollout_inst(const RolloutArgs &ra, const RolloutLaunch &lc, hipStream_t s) {
-#define LR_(RNN, W2L, GEN, SQ) \
-    hipLaunchKernelGGL((rollout_kernel<RNN, W2L, GEN, TAB, QOUT, SQ>), dim3(lc.grid), dim3(64 * kH2Waves), lc.lds, s, ra)
-#define LR2_(RNN)                                                                \
-    do {                                                                         \
-        if (lc.sq64) {                                                           \
-            LR_(RNN, true, false, 64);                                           \
-        } else if (lc.w2l) {                                                     \
-            if (lc.gen) LR_(RNN, true, true, 0); else LR_(RNN, true, false, 0);   \
-        } else {                                                                 \
-            if (lc.gen) LR_(RNN, false, true, 0); else LR_(RNN, false, false, 0); \
-        }                                                                        \
+#define LR_(RNN, W2L, GEN, SQ, PAIR)                                                                            \
+    hipLaunchKernelGGL((rollout_kernel<RNN, W2L, GEN, TAB, QOUT, SQ, PAIR>), dim3(lc.grid), dim3(64 * kH2Waves), lc.lds, \
+                       s, ra)
+#define LR2_(RNN)                                                                              \
+    do {                                                                                       \
+        if (lc.sq64 && lc.pair) {                                                              \
+            if constexpr (QOUT) return hipErrorInvalidValue; /* single-pass launches only */   \
+            else LR_(RNN, true, false, 64, true);                                              \
+        } else if (lc.sq64) {                                                                  \
+            LR_(RNN, true, false, 64, false);                                                  \
+        } else if (lc.w2l) {                                                                   \
+            if (lc.gen) LR_(RNN, true, true, 0, false); else LR_(RNN, true, false, 0, false);   \
+        } else {                                                                               \
+            if (lc.gen) LR_(RNN, false, true, 0, false); else LR_(RNN, false, false, 0, false); \
+        }                                                                                      \
     } while (0)
     if (lc.rnn) LR2_(true); else LR2_(false);
 #undef LR2_
