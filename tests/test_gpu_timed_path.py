@@ -43,6 +43,7 @@ from marl_sap_amd.controllers import REGISTRY as MAC  # noqa: E402
 from marl_sap_amd.modules.agents import RNNAgent  # noqa: E402
 from marl_sap_amd.runners import REGISTRY as RUN  # noqa: E402
 from oracle.check import bump_table_from_params, replay_all, replay_and_compare  # noqa: E402
+from oracle import philox as px  # noqa: E402
 from oracle.philox import eps_greedy_draws  # noqa: E402
 
 DEV = torch.device("cuda", 0)
@@ -98,6 +99,30 @@ def _check_invariants(b, env, E, n, m, T, prev0):
     return r
 
 
+def _check_draws(env, params, prev0, idx):
+    """The episode's draws regenerated from (seed, global env, episode 0) by oracle/philox.py:
+    every env's reset permutation, and the exported bump parameters of the sampled envs plus
+    every 257th env (scale and center bit for bit; a2 within 2^-22 relative and on the oracle's
+    width index -- tests/test_gpu_philox_draws.py derives the bound)."""
+    E, n, m, T = env.num_envs, env.n, env.m, env.T
+    g = px.global_envs(env.env_index_base, E)
+    np.testing.assert_array_equal(prev0.cpu().numpy(), px.reset_perm(env.seed_value, g, 0, n, m))
+    sel = np.unique(np.concatenate([idx, np.arange(0, E, 257)]))
+    p = params[torch.as_tensor(sel, device=DEV)].cpu().numpy()
+    active, scale, center, spread, u14, a2 = px.bump_params(env.seed_value, [g[e] for e in sel], 0, n, m, T,
+                                                            dense=env.benefits == "dense")
+    f32 = lambda x: np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)  # noqa: E731
+    assert np.array_equal(f32(p[..., 0]), f32(scale)), "bump scales differ from the oracle draw"
+    assert np.array_equal(f32(p[..., 1]), f32(center)), "bump centers differ from the oracle draw"
+    got = p[..., 2].astype(np.float64)
+    num = np.log2(np.e) * np.sqrt(-2.0 * np.log(0.05))  # a2 * spread
+    assert np.array_equal(np.rint((num / got - 3.0) / 3.0 * 16384.0).astype(np.int64), u14)
+    dev = float((np.abs(got - a2) / a2).max())
+    print(f"oracle draws: {E} permutations, {len(sel)} envs' parameters ({active.size} pairs), "
+          f"largest a2 deviation {dev * 2 ** 22:.3f} * 2^-22")
+    assert dev <= 2.0 ** -22
+
+
 def _check_actions(b, mac, idx, n, m, T, eps, seed, counter0):
     """Replay the PyTorch RNNAgent over the sampled envs' observation rows; predicted
     action = the Philox exploration draw or the greedy argmax (gap-tolerant)."""
@@ -142,8 +167,9 @@ def test_bench_workload_episode_vs_oracle(config):
         b = runner.run(test_mode=False)
         assert runner.t_env == E * T
         # the reset ran inside the episode's launch (asg_reset_rollout): its permutation is the
-        # batch's prev_assigns row 0 (no quirks here; checked to be a partial permutation below),
-        # its Philox episode key the handle's until the next reset
+        # batch's prev_assigns row 0 (no quirks here; checked to be a partial permutation below and
+        # to be the oracle's draw in _check_draws), its Philox episode key the handle's until the
+        # next reset
         prev0 = b["prev_assigns"][:, 0].reshape(E, n).clone()
         pz = prev0.sort(dim=1).values
         assert bool(((pz >= 0) & (pz < m)).all()) and bool((pz[:, 1:] != pz[:, :-1]).all())
@@ -151,6 +177,7 @@ def test_bench_workload_episode_vs_oracle(config):
         env.sync()
         r = _check_invariants(b, env, E, n, m, T, prev0)
         idx = _sample(E)
+        _check_draws(env, params, prev0, idx)
         table = bump_table_from_params(params[idx].cpu().numpy(), T)
         td = {k: v[idx].cpu().numpy() for k, v in b.data.transition_data.items()}
         replay_and_compare(n, m, T, L, 0.5, table, prev0[idx].cpu().numpy(), td, r[idx].cpu().numpy(),
