@@ -44,6 +44,12 @@
  *                              mock_constellation_reda.yaml / mock_constellation_iql.yaml), as
  *                              learners/q_learner.py:67-85 and sap_q_learner.py:69-84 run it;
  *                              asg_mlp_agent_unroll_backward = autograd's way back through it
+ *   asg_mlp_agent_unroll_ids   ACCritic.forward over every row of a batch (modules/critics/ac.py:6-50)
+ *   asg_bids_log_prob          ContinuousPPOLearner.train's Gaussian log-probability of the stored
+ *                              bids (learners/cont_ppo_learner.py:66-75, :91-93)
+ *   asg_ppo_bids_loss          its clipped surrogate and the gradient autograd takes back to the
+ *                              logits (learners/cont_ppo_learner.py:91-105)
+ *   asg_nstep_returns          ContinuousPPOLearner.nstep_returns (learners/cont_ppo_learner.py:174-192)
  *   asg_get_returns            the runners' episode_return accumulation
  *                              (episode_runner.py:84, parallel_runner.py:173-176)
  *   asg_filtered_*             FilteredSAPActionSelector / FilteredEpsGrSAPTestActionSelector
@@ -394,6 +400,60 @@ int asg_mlp_agent_unroll(const float *x, const int64_t x_strides[3], int T1, int
 int asg_mlp_agent_unroll_backward(const float *dh_q, const float *h_all, const float *x1_save,
                                   const float *W_r, int64_t N, int hidden, float *dh, float *dx1,
                                   void *hip_stream);
+/* asg_mlp_agent_unroll with the reference critics' agent-id inputs (modules/critics/ac.py:32-43):
+ * W1 is [64][K + n] contiguous; row (t, env, agent) starts fc1 from b1 + W1[:, K + agent].
+ * The [obs, eye(n)] concatenation is never built: x is the observation alone, as above, and the
+ * same kernel source runs with the W1 row stride K + n (float4 loads of W1 when K % 4 == 0 and
+ * (K + n) % 4 == 0).  The network is ACCritic's: W_r = fc2, W2 = fc3, n_out = m or 1.  Same
+ * outputs, checks and determinism as asg_mlp_agent_unroll; asg_mlp_agent_unroll_backward is its
+ * backward pass too (dW1[:, :K] = dx1^T x, dW1[:, K:] = the per-agent sums of dx1). */
+int asg_mlp_agent_unroll_ids(const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
+                             const float *W1, const float *W_r, const float *W2, const float *b1,
+                             const float *b_r, const float *b2, int hidden, int n_out, float *q,
+                             float *h_all, float *x1_save, void *hip_stream);
+
+/* ---- the loss side of ContinuousPPOLearner.train (learners/cont_ppo_learner.py:48-192) -----
+ * All three work on [T][R][m] buffers in the unroll kernels' flattened time-major row order
+ * (row = t * R + env * n + agent, R = B * n, contiguous, 16-B aligned), so the agent's logits,
+ * the critic's values, the advantages and the gradients are used with no permute copy; what the
+ * EpisodeBatch holds (the bids in batch["actions"], the rewards, the (b, t) mask; float32) is read
+ * through element strides {t, env, agent} (0 where a tensor has no such dim).  1 <= m <= 512.
+ * No atomics and a fixed reduction order: the same inputs give the same bits.
+ * ASG_E_INVALID_ARG before any device call when m is outside 1..512, T < 1, B * n < 1, sigma <= 0,
+ * nsteps < 1, a required pointer is NULL or a pointer is misaligned.
+ *
+ * asg_bids_log_prob: ContinuousActionSelector.action_log_prob as the learner calls it (:75, :93;
+ * arguments swapped, the Gaussian is symmetric in them):
+ *     pi = softmax(logits[row]) (row_softmax) or logits[row];  pi = 1 where mask(b, t) == 0 (:73)
+ *     logp[row][j] = -(pi_j - bids_j)^2 / (2 sigma^2) - ln sigma - ln sqrt(2 pi) */
+int asg_bids_log_prob(const float *logits, const float *bids, const int64_t bid_strides[3],
+                      const float *mask, const int64_t mask_strides[3], int T, int64_t B, int n, int m,
+                      double sigma, int row_softmax, float *logp, void *hip_stream);
+/* One epoch's clipped surrogate (:91-101) and its gradient in one launch.  With pi and logp as
+ * above, ratio = exp(logp - old_logp), s1 = ratio A, s2 = clamp(ratio, 1 - eps, 1 + eps) A:
+ *     partial[g]  = the sum of min(s1, s2) mask over the ASG_PPO_ROWS_PER_GROUP rows of workgroup g
+ *                   (ceil(T R / ASG_PPO_ROWS_PER_GROUP) floats); loss = -sum(partial) * inv_count
+ *     g_j         = -mask inv_count [s1 <= s2] A_j ratio_j (-(pi_j - bids_j) / sigma^2)
+ *     dlogits[j]  = pi_j (g_j - sum_k g_k pi_k) (row_softmax) or g_j: d loss / d logits, exactly
+ *                   what autograd gives through th.min and th.clamp; zero on masked rows
+ *     row_max     = max_j pi_j per row, [T R], when not NULL (the "max bid" statistic, :130)
+ * inv_count: one float on the device, 1 / mask.sum() over the expanded [B, T, n, m] mask. */
+#define ASG_PPO_ROWS_PER_GROUP 16
+int asg_ppo_bids_loss(const float *logits, const float *bids, const int64_t bid_strides[3],
+                      const float *old_logp, const float *adv, const float *mask,
+                      const int64_t mask_strides[3], int T, int64_t B, int n, int m, double sigma,
+                      double eps_clip, const float *inv_count, int row_softmax, float *partial,
+                      float *dlogits, float *row_max, void *hip_stream);
+/* nstep_returns (:174-192) in one launch: values [T + 1][R][m], rewards [B, T, n] and the mask
+ * strided (the reference's x m repeat of both is never built), out [T][R][m].  Per element the
+ * reference's loop over step = 0 .. nsteps with its three branches: the bootstrap value
+ * gamma^nsteps values[t] mask[t] at step == nsteps; on the last row with add_value_last_step the
+ * masked reward plus gamma^(step + 1) values[t + 1], unmasked; else gamma^step rewards[t] mask[t].
+ * gamma^k is evaluated in double on the host and rounded to float32, as torch applies a Python
+ * scalar to a float32 tensor.  min(nsteps, T - 1) <= 254. */
+int asg_nstep_returns(const float *values, const float *rewards, const int64_t reward_strides[3],
+                      const float *mask, const int64_t mask_strides[3], int T, int64_t B, int n, int m,
+                      double gamma, int nsteps, int add_value_last_step, float *out, void *hip_stream);
 
 /* ---- filtered selectors (the real-env algorithms' action_selector) -------------------------
  * The agent emits M + 1 values per agent: its top-M tasks by total benefit and a baseline.

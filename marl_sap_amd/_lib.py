@@ -46,7 +46,9 @@ EXPORTS = ["asg_abi_version", "asg_last_error", "asg_create", "asg_destroy", "as
            "asg_sap_noise", "asg_random_rollout", "asg_sap_select_warm", "asg_bids_select",
            "asg_reset_forward", "asg_step_ex", "asg_step_forward_ex", "asg_bids_select_count",
            "asg_rnn_agent_unroll", "asg_rnn_agent_unroll_backward", "asg_mlp_agent_unroll",
-           "asg_mlp_agent_unroll_backward"]
+           "asg_mlp_agent_unroll_backward", "asg_mlp_agent_unroll_ids", "asg_bids_log_prob", "asg_ppo_bids_loss",
+           "asg_nstep_returns"]
+ASG_PPO_ROWS_PER_GROUP = 16
 
 
 class AsgField(ctypes.Structure):
@@ -144,6 +146,12 @@ def lib():
         if hasattr(L, "asg_mlp_agent_unroll"):
             L.asg_mlp_agent_unroll.argtypes = [vp, i64p, i32, i64, i32, i32] + [vp] * 6 + [i32, i32, vp, vp, vp, vp]
             L.asg_mlp_agent_unroll_backward.argtypes = [vp] * 4 + [i64, i32, vp, vp, vp]
+        if hasattr(L, "asg_mlp_agent_unroll_ids"):
+            L.asg_mlp_agent_unroll_ids.argtypes = L.asg_mlp_agent_unroll.argtypes
+            L.asg_bids_log_prob.argtypes = [vp, vp, i64p, vp, i64p, i32, i64, i32, i32, dbl, i32, vp, vp]
+            L.asg_ppo_bids_loss.argtypes = [vp, vp, i64p, vp, vp, vp, i64p, i32, i64, i32, i32, dbl, dbl, vp, i32, vp,
+                                            vp, vp, vp]
+            L.asg_nstep_returns.argtypes = [vp, vp, i64p, vp, i64p, i32, i64, i32, i32, dbl, i32, i32, vp, vp]
         L.asg_real_create.argtypes = [ctypes.POINTER(AsgRealConfig), i32, vp, ctypes.POINTER(vp)]
         L.asg_real_destroy.argtypes = [vp]
         L.asg_real_destroy.restype = None

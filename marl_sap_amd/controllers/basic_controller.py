@@ -192,14 +192,18 @@ class BasicMAC:
             agent_outs = torch.nn.functional.softmax(agent_outs, dim=-1)
         return agent_outs.view(ep_batch.batch_size, self.n, -1)
 
-    def forward_sequence(self, ep_batch):
+    def forward_sequence(self, ep_batch, rows=None):
         """forward() over every row of the batch, as the learners call it (reference
         learners/sap_q_learner.py:69-84): init_hidden, then t = 0 .. max_seq_length - 1.
         Returns [B, T1, n, n_out] and leaves hidden_states as those calls would.  The agent's
-        unroll() runs the sequence (one launch for the fused GRU agent)."""
+        unroll() runs the sequence (one launch for the fused GRU agent).  rows: only the first
+        `rows` rows (learners/cont_ppo_learner.py:68, :80 stop at max_seq_length - 1)."""
         bs = ep_batch.batch_size
         self.init_hidden(bs)
-        agent_outs, self.hidden_states = self.agent.unroll(self._build_sequence_inputs(ep_batch), None)
+        inputs = self._build_sequence_inputs(ep_batch)
+        if rows is not None:
+            inputs = inputs[:, :rows]
+        agent_outs, self.hidden_states = self.agent.unroll(inputs, None)
         if self.agent_output_type == "pi_logits":
             agent_outs = torch.nn.functional.softmax(agent_outs, dim=-1)
         return agent_outs

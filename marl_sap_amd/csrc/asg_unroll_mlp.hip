@@ -9,7 +9,9 @@
 // own (t, env, agent).
 //
 //   mlp_fwd_kernel : x1 = relu(W1 x + b1); h = relu(W_r x1 + b_r); q = W2 h + b2 per row.
-//                    Writes q, h (h_all) and, for the backward pass, x1.
+//                    Writes q, h (h_all) and, for the backward pass, x1.  A second instance
+//                    (asg_mlp_agent_unroll_ids) is the reference's ACCritic, whose input is
+//                    [obs, eye(n)]: W1 is [64][K + n] and the one-hot block a column gather.
 //   mlp_bwd_kernel : dh = dh_q . (h > 0); dx1 = (dh @ W_r) . (x1 > 0) per row.  The parameter
 //                    gradients are plain GEMMs over the N rows and stay in PyTorch.
 //
@@ -40,6 +42,10 @@ struct MlpFwdArgs {
     int xvec, w1vec;
 };
 
+// kIds: the reference critics' agent-id inputs (modules/critics/ac.py:32-43) -- W1 is [64][K + n]
+// and the one-hot block of row (t, env, agent) is the column gather W1[:, K + agent], added to
+// the bias before the K observation inputs are accumulated; the concatenation is never read.
+template <bool kIds>
 __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
     __shared__ float sWr[kHid * kWS];
     for (int i = threadIdx.x; i < kHid * (kHid / 4); i += blockDim.x) {
@@ -62,6 +68,7 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
     const int K = a.K, nk = (K + 15) / 16, nout = a.nout, nct = (nout + 15) / 16;
     const bool xvec = a.xvec != 0, w1vec = a.w1vec != 0, qvec = (nout & 3) == 0;
     const int64_t base = rc * kHid;
+    const int64_t ldw = kIds ? (int64_t)K + a.n : (int64_t)K;  // W1 row stride
 
     // ---- fc1: x1^T = relu(W1 x^T + b1) ----
     f32x4 x1[4];
@@ -69,6 +76,13 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
         f32x4 acc[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) acc[mt] = ld4(a.b1 + 16 * mt + 4 * qd);
+        if constexpr (kIds) {
+            const float *wid = a.W1 + K + ag;  // column K + agent of every W1 row
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[mt][v] += wid[(int64_t)(16 * mt + 4 * qd + v) * ldw];
+        }
         // two register buffers of kFc1G k-chunks each: one is refilled from L2 / HBM under the
         // MFMAs of the other; chunks past K load nothing (ldk) and are skipped
         f32x4 xa[kFc1G], wa[kFc1G][4], xb[kFc1G], wb[kFc1G][4];
@@ -78,7 +92,7 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
                 const int k = 16 * (kc0 + g) + 4 * qd;
                 xv[g] = ldk(xr, k, K, xvec);
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) w[g][mt] = ldk(a.W1 + (int64_t)(16 * mt + r) * K, k, K, w1vec);
+                for (int mt = 0; mt < 4; ++mt) w[g][mt] = ldk(a.W1 + (int64_t)(16 * mt + r) * ldw, k, K, w1vec);
             }
             __builtin_amdgcn_sched_barrier(0);  // issue the loads here, not next to their use
         };
@@ -212,23 +226,26 @@ constexpr int64_t kMaxRows = (int64_t)0x7fffffff * 16 * kWaves;  // the grid's x
 }  // namespace
 }  // namespace asg
 
-extern "C" int asg_mlp_agent_unroll(const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
-                                    const float *W1, const float *W_r, const float *W2, const float *b1,
-                                    const float *b_r, const float *b2, int hidden, int n_out, float *q, float *h_all,
-                                    float *x1_save, void *hip_stream) {
-    using namespace asg;
+namespace asg {
+namespace {
+
+template <bool kIds>
+int mlp_unroll(const char *who, const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
+               const float *W1, const float *W_r, const float *W2, const float *b1, const float *b_r,
+               const float *b2, int hidden, int n_out, float *q, float *h_all, float *x1_save, void *hip_stream) {
+    const std::string w(who);
     const int64_t R = (B > 0 && n > 0) ? B * n : 0;
-    if (hidden != 64) return fail("asg_mlp_agent_unroll: hidden must be 64");
-    if (n_out < 1 || n_out > 512) return fail("asg_mlp_agent_unroll: n_out must be in 1..512");
-    if (T1 < 1) return fail("asg_mlp_agent_unroll: T1 must be >= 1");
-    if (R < 1) return fail("asg_mlp_agent_unroll: needs at least one agent row");
-    if (K < 1) return fail("asg_mlp_agent_unroll: K must be >= 1");
-    if (R > kMaxRows / T1) return fail("asg_mlp_agent_unroll: too many rows");
+    if (hidden != 64) return fail((w + ": hidden must be 64").c_str());
+    if (n_out < 1 || n_out > 512) return fail((w + ": n_out must be in 1..512").c_str());
+    if (T1 < 1) return fail((w + ": T1 must be >= 1").c_str());
+    if (R < 1) return fail((w + ": needs at least one agent row").c_str());
+    if (K < 1) return fail((w + ": K must be >= 1").c_str());
+    if (R > kMaxRows / T1) return fail((w + ": too many rows").c_str());
     if (!x || !x_strides || !W1 || !W_r || !W2 || !b1 || !b_r || !b2 || !q || !h_all)
-        return fail("asg_mlp_agent_unroll: NULL argument");
+        return fail((w + ": NULL argument").c_str());
     if (!al(x, 4) || !al(W1, 4) || !al(b2, 4) || !al(W_r, 16) || !al(W2, 16) || !al(b1, 16) || !al(b_r, 16) ||
         !al(q, 16) || !al(h_all, 16) || !al(x1_save, 16))
-        return fail("asg_mlp_agent_unroll: misaligned pointer (16 B for W_r, W2, b1, b_r, q, h_all, x1_save)");
+        return fail((w + ": misaligned pointer (16 B for W_r, W2, b1, b_r, q, h_all, x1_save)").c_str());
     MlpFwdArgs a;
     a.x = x;
     a.xs_t = x_strides[0];
@@ -249,11 +266,33 @@ extern "C" int asg_mlp_agent_unroll(const float *x, const int64_t x_strides[3], 
     a.h_all = h_all;
     a.x1_save = x1_save;
     a.xvec = K % 4 == 0 && al(x, 16) && ((a.xs_t | a.xs_e | a.xs_a) & 3) == 0;
-    a.w1vec = K % 4 == 0 && al(W1, 16);
+    // 16-B loads of a W1 row's first K entries: the row stride (K, or K + n with the id block)
+    // and K are both multiples of 4
+    a.w1vec = K % 4 == 0 && (!kIds || (K + n) % 4 == 0) && al(W1, 16);
     const unsigned grid = (unsigned)((a.N + 16 * kWaves - 1) / (16 * kWaves));
-    hipLaunchKernelGGL(mlp_fwd_kernel, dim3(grid), dim3(64 * kWaves), 0, static_cast<hipStream_t>(hip_stream), a);
+    hipLaunchKernelGGL(mlp_fwd_kernel<kIds>, dim3(grid), dim3(64 * kWaves), 0, static_cast<hipStream_t>(hip_stream),
+                       a);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ASG_OK : hip_fail(e, "asg_mlp_agent_unroll");
+    return e == hipSuccess ? ASG_OK : hip_fail(e, who);
+}
+
+}  // namespace
+}  // namespace asg
+
+extern "C" int asg_mlp_agent_unroll(const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
+                                    const float *W1, const float *W_r, const float *W2, const float *b1,
+                                    const float *b_r, const float *b2, int hidden, int n_out, float *q, float *h_all,
+                                    float *x1_save, void *hip_stream) {
+    return asg::mlp_unroll<false>("asg_mlp_agent_unroll", x, x_strides, T1, B, n, K, W1, W_r, W2, b1, b_r, b2, hidden,
+                                  n_out, q, h_all, x1_save, hip_stream);
+}
+
+extern "C" int asg_mlp_agent_unroll_ids(const float *x, const int64_t x_strides[3], int T1, int64_t B, int n, int K,
+                                        const float *W1, const float *W_r, const float *W2, const float *b1,
+                                        const float *b_r, const float *b2, int hidden, int n_out, float *q,
+                                        float *h_all, float *x1_save, void *hip_stream) {
+    return asg::mlp_unroll<true>("asg_mlp_agent_unroll_ids", x, x_strides, T1, B, n, K, W1, W_r, W2, b1, b_r, b2,
+                                 hidden, n_out, q, h_all, x1_save, hip_stream);
 }
 
 extern "C" int asg_mlp_agent_unroll_backward(const float *dh_q, const float *h_all, const float *x1_save,

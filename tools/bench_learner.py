@@ -20,8 +20,22 @@ step of both paths, their spread (max - min over the repeats), the ratio, and th
 backward kernel times alone.  `faster` is true when the fused median beats the unfused one
 by more than the unfused path's own spread.
 
+--learner cont_ppo_learner times ContinuousPPOLearner.train (ippo_sap.yaml: the Linear agent on
+pi_logits, the continuous selector on the bids schedule filling the buffer, ACCritic, 4 epochs,
+q_nstep 5; --episodes defaults to the config's batch_size, 10) three ways, alternating:
+
+  fused      everything on the kernels: the agent and critic unrolls, asg_nstep_returns,
+             asg_bids_log_prob, asg_ppo_bids_loss
+  torch_loss fused_ppo = False with fused_linear_unroll: the agent unroll on its kernels, the
+             critic, the n-step loop and the loss in PyTorch
+  reference  fused_ppo = False and the per-step agent loop (unfused_unroll): the reference's
+             formulation, the baseline
+
+and reports the device activities (kernel launches and copies, from torch.profiler) of one
+train() of each.
+
     python tools/bench_learner.py [--repeats 10] [--warmup 3] [--episodes 32]
-                                  [--learner sap_q_learner|q_learner] [--use-rnn 1|0]
+                                  [--learner sap_q_learner|q_learner|cont_ppo_learner] [--use-rnn 1|0]
 """
 import argparse
 import ctypes
@@ -52,18 +66,95 @@ def timed(fn, repeats):
 kInner = 20  # launches per sample of the Linear agent's kernels timed alone
 
 
+def device_activities(fn):
+    """Kernel launches and copies on the device during fn(), from torch.profiler; None where
+    the profiler is not available."""
+    try:
+        from torch.autograd import DeviceType
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        return sum(e.count for e in prof.key_averages() if e.device_type == DeviceType.CUDA) or None
+    except Exception as e:  # noqa: BLE001
+        print(f"launch count unavailable: {e!r}", file=sys.stderr)
+        return None
+
+
+def main_ppo(o):
+    from marl_sap_amd.components import ReplayBuffer
+    from marl_sap_amd.controllers import REGISTRY as mac_REGISTRY
+    from marl_sap_amd.learners import REGISTRY as le_REGISTRY
+    from marl_sap_amd.runners import REGISTRY as r_REGISTRY
+
+    dev = torch.device("cuda", 0)
+    E, n, T = o.episodes, o.n, o.T
+    a = bench.parse(["--n", str(n), "--m", str(n), "--T", str(T), "--cpu-baseline", "0", "--secondary", "0"])
+    args = bench.make_args(
+        a, E, selector="bids", agent="rnn", fused_linear_unroll=True, reuse_batch=False, lr=3e-4, gamma=0.99,
+        grad_norm_clip=10.0, critic_type="ac_critic", epochs=4, eps_clip=0.2, q_nstep=5, add_value_last_step=True,
+        target_update_interval_or_tau=0.01, standardise_rewards=True, standardise_returns=False,
+        learner_log_interval=10 ** 12, use_mps_action_selection=False, unfused_unroll=False, fused_ppo=True)
+    runner = r_REGISTRY["gpu"](args, bench.NullLogger())
+    env = runner.get_env()
+    torch.manual_seed(a.seed)
+    mac = mac_REGISTRY["basic_mac"](env.scheme, {"agents": n}, args)
+    mac.to(dev)
+    runner.setup(env.scheme, {"agents": n}, env.preprocess, mac)
+    learner = le_REGISTRY[o.learner](mac, env.scheme, bench.NullLogger(), args)
+    learner.log_stats_t = 0  # no logging branch (its .item() calls) in the timed steps
+    buf = ReplayBuffer(env.scheme, {"agents": n}, E, T + 1, preprocess=env.preprocess, device=dev)
+    buf.insert_episode_batch(runner.run(test_mode=False))
+    batch = buf.sample(E, rng=np.random.RandomState(a.seed))
+    legs = {"fused": (True, False), "torch_loss": (False, False), "reference": (False, True)}
+    step = [0]
+
+    def train(leg):
+        args.fused_ppo, args.unfused_unroll = legs[leg]
+        learner.train(batch, step[0], step[0])
+        step[0] += 1
+
+    for _ in range(o.warmup):
+        for leg in legs:
+            train(leg)
+    times = {leg: [] for leg in legs}
+    for _ in range(o.repeats):  # alternating, so drift hits all alike
+        for leg in legs:
+            times[leg] += timed(lambda: train(leg), 1)
+    launches = {leg: device_activities(lambda: train(leg)) for leg in legs}
+    med = {leg: statistics.median(v) for leg, v in times.items()}
+    spread = {leg: max(v) - min(v) for leg, v in times.items()}
+    K = mac._build_sequence_inputs(batch).shape[-1]
+    out = {"metric": o.learner + "_train_ms", "shape": {"episodes": E, "n": n, "m": n, "L": a.L, "T": T, "K": K,
+                                                        "epochs": args.epochs, "q_nstep": args.q_nstep},
+           "repeats": o.repeats}
+    for leg in legs:
+        out[leg + "_ms"] = round(med[leg], 4)
+        out[leg + "_spread_ms"] = round(spread[leg], 4)
+        out[leg + "_device_activities"] = launches[leg]
+    out["ratio_reference_over_fused"] = round(med["reference"] / med["fused"], 3)
+    out["ratio_torch_loss_over_fused"] = round(med["torch_loss"] / med["fused"], 3)
+    out["faster"] = bool(med["reference"] - med["fused"] > spread["reference"])
+    print(json.dumps(out))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--repeats", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--episodes", type=int, default=32)
+    p.add_argument("--episodes", type=int, default=None)
     p.add_argument("--n", type=int, default=64)
     p.add_argument("--T", type=int, default=20)
-    p.add_argument("--learner", default="sap_q_learner", choices=["sap_q_learner", "q_learner"])
+    p.add_argument("--learner", default="sap_q_learner", choices=["sap_q_learner", "q_learner", "cont_ppo_learner"])
     p.add_argument("--use-rnn", type=int, default=1, choices=[1, 0])
     o = p.parse_args()
     if o.repeats < 5:
         p.error("--repeats must be at least 5")
+    if o.episodes is None:
+        o.episodes = 10 if o.learner == "cont_ppo_learner" else 32
+    if o.learner == "cont_ppo_learner":
+        return main_ppo(o)
     from marl_sap_amd import _lib
     from marl_sap_amd.components import ReplayBuffer
     from marl_sap_amd.controllers import REGISTRY as mac_REGISTRY
