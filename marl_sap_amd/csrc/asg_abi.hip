@@ -10,6 +10,7 @@
 #include "../../include/asg.h"
 #include "asg_internal.h"
 
+using asg::DeviceGuard;
 using asg::EnvState;
 
 struct asg_handle {
@@ -42,19 +43,6 @@ int fail(asg_handle *h, int code, const std::string &msg) {
 int hip_fail(asg_handle *h, hipError_t e, const char *what) {
     return fail(h, ASG_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-
-// keeps the caller's current device (PyTorch tracks its own) around every entry point
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 bool field_ok(const asg_field &f, int want_dtype) { return f.ptr == nullptr || f.dtype == want_dtype; }
 

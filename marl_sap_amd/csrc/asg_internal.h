@@ -13,6 +13,19 @@ namespace asg {
 // the thread-local message returned by asg_last_error(NULL) (asg_abi.hip)
 void set_last_error(const std::string &msg);
 
+// keeps the caller's current device (PyTorch tracks its own) around every entry point
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
 struct EnvState {
     int64_t E;             // envs in this handle
     int n, m, T, L;
