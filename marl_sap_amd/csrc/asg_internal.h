@@ -69,8 +69,8 @@ struct SelectArgs {
     int *err;              // sticky: exploration over a row with no available action
 };
 
+// mock env (asg_env.hip)
 hipError_t launch_reset(const asg_batch_view &bv, const EnvState &st, int ts, bool construct, hipStream_t s);
-hipError_t launch_reset_draws(const EnvState &st, bool construct, hipStream_t s);
 // bids_as_actions: assign_ready = st.assign already holds LSA(bids row ts) (asg_bids_select)
 hipError_t launch_step(const asg_batch_view &bv, const EnvState &st, int ts, int k, hipStream_t s,
                        bool assign_ready = false);
@@ -83,9 +83,14 @@ hipError_t launch_export_table(const EnvState &st, double *out, hipStream_t s);
 hipError_t launch_export_bump_params(const EnvState &st, float *out, hipStream_t s);
 hipError_t launch_import_table(const double *in, int64_t src_envs, const EnvState &st, hipStream_t s);
 hipError_t launch_export_prev(const EnvState &st, int64_t *out, hipStream_t s);
+
+// the mock env's MT19937 streams (asg_env_mt.hip); launch_reset_draws: the MT19937 mode's reset
+// without its row write (the permutation, and the table unless it is injected)
+hipError_t launch_reset_draws(const EnvState &st, bool construct, hipStream_t s);
 hipError_t launch_mt_seed(const EnvState &st, hipStream_t s);
 hipError_t launch_mt_advance(const EnvState &st, int64_t words, hipStream_t s);
 
+// LSA, beta_hat and the selectors (asg_lsa.hip, asg_select.hip)
 hipError_t launch_lsa_batched(const void *C, int dtype, const int64_t strides[3], int64_t B, int nr, int nc,
                               int maximize, int64_t *row_out, int64_t *col_out, int32_t *status_out,
                               hipStream_t s);

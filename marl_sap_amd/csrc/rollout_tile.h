@@ -56,7 +56,7 @@ struct RolloutArgs {
     const double2 *par;    // the MT19937 reset's draws: rewards evaluated from them (mt_par_value)
     const float *table32;  // the benefits rounded to float32: the lookahead rows' reads
     // MT19937 draws: table32 is COMPACT (per (env, t) slice the bump pairs only, (agent, task)
-    // order; asg_env.hip:mt_table_kernel): their masks [E][n][W] and each word's first index
+    // order; asg_env_mt.hip:mt_table_kernel): their masks [E][n][W] and each word's first index
     const uint64_t *tmask;
     const int *toff;
     // QOUT instances: the agent's Q rows [E n][m] f32 (the forward of asg_rnn_agent_forward)

@@ -222,6 +222,39 @@ def test_mt_multi_env_streams(replicate):
             np.testing.assert_array_equal(prev[e], oe.prev_assigns)
 
 
+def _check_stream_skip(calls):
+    """advance_stream(w) for w in calls, then two resets: with an injected table neither
+    construction nor reset draws benefits (mock :32-37), so each reset's prev_assigns is
+    permutation(m)[:n] drawn right after the skipped words -- and the second one checks that the
+    state the kernels hand back is numpy's."""
+    n, m, T, L, s, E = 4, 6, 2, 1, 31, 3
+    env = AssignEnvBatch(n, m, T, L, 0.5, seed=s, sat_prox_mat=np.zeros((n, m, T)), num_envs=E, device=DEV,
+                         rng="mt19937")
+    for w in calls:
+        env.advance_stream(w)
+    mts = [ora.MT(s + e) for e in range(E)]
+    for mt in mts:
+        mt.next32(sum(calls))
+    b = new_batch(env, E)
+    for reset in range(2):
+        env.reset(b, 0)
+        prev = env.export_prev_assigns().cpu().numpy()
+        for e in range(E):
+            np.testing.assert_array_equal(prev[e], mts[e].permutation(m)[:n], err_msg=f"env {e}, reset {reset}")
+    return prev
+
+
+# a fresh stream has pos = 624: these put the permutation's first word before, on and after a
+# block edge, one and several twists in
+@pytest.mark.parametrize("w", [0, 1, 623, 624, 625, 1247, 1248, 2000])
+def test_mt_stream_skip(w):
+    _check_stream_skip((w,))
+
+
+def test_mt_stream_skip_two_calls():
+    np.testing.assert_array_equal(_check_stream_skip((600, 100)), _check_stream_skip((700,)))
+
+
 @pytest.mark.parametrize("n,m,T,L", [(12, 16, 8, 3), (64, 64, 20, 3), (5, 9, 6, 2)])
 def test_mt_generated_steps_exact_on_export(n, m, T, L):
     """Same-seed mode keeps no float64 table: the rows come from the reset's float32 table and

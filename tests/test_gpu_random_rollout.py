@@ -38,6 +38,12 @@ def split_episode(env, b, T):
         env.step(b, t)
 
 
+def sparse_table(n, m, T):
+    """An injected [n, m, T] table with about three quarters of its entries 0."""
+    rng = np.random.RandomState(1000 * n + m)
+    return rng.uniform(size=(n, m, T)) * (rng.uniform(size=(n, m, T)) > 0.75)
+
+
 @pytest.mark.parametrize("n,m,E,T,L,chunks,time_major,kw", [
     (16, 16, 512, 20, 3, (20,), True, {}),              # configs[1]'s shape, one launch per episode
     (16, 16, 256, 20, 3, (7, 1, 12), True, {}),          # chunked launches
@@ -46,16 +52,26 @@ def split_episode(env, b, T):
     (33, 41, 40, 9, 0, (9,), True, {}),                  # L = 0: no lookahead blocks
     (16, 16, 128, 12, 3, (12,), True, {"benefits": "dense"}),
     (16, 16, 64, 10, 3, (10,), True, {"quirks": ("prev_assigns_zero", "parallel_terminated")}),
+    # the table sources on the episode launch: the MT19937 draws (ParSrc; the launch continues
+    # after asg_reset, which the ABI requires in that mode) and an injected table under Philox
+    # (TableSrc), each on the vector (m % 4 == 0) and the scalar row writer
+    (12, 16, 5, 8, 3, (8,), True, {"rng": "mt19937"}),
+    (5, 9, 4, 6, 2, (6,), True, {"rng": "mt19937"}),
+    (12, 16, 5, 8, 3, (3, 5), True, {"sat_prox_mat": sparse_table(12, 16, 8)}),
+    (5, 9, 4, 6, 2, (6,), True, {"sat_prox_mat": sparse_table(5, 9, 6)}),
 ])
 def test_random_rollout_equals_split_launches(n, m, E, T, L, chunks, time_major, kw):
     a = AssignEnvBatch(n, m, T, L, 0.5, seed=77, num_envs=E, device=DEV, **kw)
     f = AssignEnvBatch(n, m, T, L, 0.5, seed=77, num_envs=E, device=DEV, **kw)
+    launch_resets = kw.get("rng") != "mt19937"
     for episode in range(2):  # the second episode: a fresh Philox key, as asg_reset's
         ba, bf = new_batch(a, E, time_major), new_batch(f, E, time_major)
         split_episode(a, ba, T)
+        if not launch_resets:
+            f.reset(bf, 0)
         t = 0
         for i, s in enumerate(chunks):
-            done = f.random_rollout(bf, t, s, reset=(i == 0))
+            done = f.random_rollout(bf, t, s, reset=(launch_resets and i == 0))
             t += s
             assert done == (t >= T)
         a.sync()

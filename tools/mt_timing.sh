@@ -1,8 +1,11 @@
 #!/bin/bash
 # Where the same-seed reset's draw kernel spends its time: kernel traces of the compat leg
-# (bench.py --rng mt19937) with the timing-only builds of tools' ASG_MT_XSKIP bits (WRONG results):
-#   for v in 1 2 4; do python -m marl_sap_amd.build --out build/mtx$v.so -DASG_TIMING_EXPERIMENTS \
+# (bench.py --rng mt19937) with the timing-only builds of the ASG_MT_XSKIP bits (WRONG results).
+# The switch left the sources after commit 324bfaf, so the variants are built from that commit:
+#   for v in 1 2 4; do bash tools/build_rev.sh 324bfaf build/mtx$v.so -DASG_TIMING_EXPERIMENTS \
 #       -DASG_MT_XSKIP=$v; done        (CPU side), then on the GPU box: bash tools/mt_timing.sh OUT_DIR
+# ("default" below is then the in-tree library, not the same commit's: build 324bfaf without flags
+# for a like-for-like baseline)
 set -o pipefail
 OUT=${1:?out dir}
 mkdir -p "$OUT"
