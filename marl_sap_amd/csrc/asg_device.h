@@ -255,9 +255,6 @@ __device__ __forceinline__ T wave_allreduce(T v, Op op) {
 __device__ __forceinline__ double wave_min_f64(double v) {
     return wave_allreduce(v, [](double a, double b) { return fmin(a, b); });
 }
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-    return wave_allreduce(v, [](uint64_t a, uint64_t b) { return a > b ? a : b; });
-}
 __device__ __forceinline__ int wave_max_i32(int v) {
     return wave_allreduce(v, [](int a, int b) { return a > b ? a : b; });
 }
@@ -271,7 +268,6 @@ __device__ __forceinline__ int wave_or_i32(int v) {
 // into lane 63.  s_nop 1 covers the VALU-write -> DPP-read hazard.  Call in wave-uniform
 // control flow.
 __device__ __forceinline__ float wave_min_f32_nonan(float x0) {
-#ifndef ASG_LSA_PERMLANE_MIN
     float x;  // a separate result register: the input stays live without a copy
     asm("s_nop 1\n\t"
         "v_min_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
@@ -288,29 +284,6 @@ __device__ __forceinline__ float wave_min_f32_nonan(float x0) {
         : "=&v"(x)
         : "v"(x0));
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-#else
-    const float x = x0;
-    float y, t;
-    asm("s_nop 1\n\t"
-        "v_min_f32_dpp %0, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_mov_b32 %1, %0\n\t"
-        "s_nop 1\n\t"
-        "v_permlane16_swap_b32 %0, %1\n\t"
-        "v_min_f32 %0, %0, %1\n\t"
-        "v_mov_b32 %1, %0\n\t"
-        "s_nop 1\n\t"
-        "v_permlane32_swap_b32 %0, %1\n\t"
-        "v_min_f32 %0, %0, %1"
-        : "=&v"(y), "=&v"(t)
-        : "v"(x));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, y)));
-#endif
 }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return wave_allreduce(v, [](uint32_t a, uint32_t b) { return a > b ? a : b; });

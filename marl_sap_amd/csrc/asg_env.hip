@@ -17,6 +17,7 @@
 #include "asg_device.h"
 #include "asg_internal.h"
 #include "env_src.h"
+#include "lsa_reg64.h"
 #include "lsa_wave.h"
 
 namespace asg {

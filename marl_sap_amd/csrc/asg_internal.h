@@ -90,7 +90,7 @@ hipError_t launch_reset_draws(const EnvState &st, bool construct, hipStream_t s)
 hipError_t launch_mt_seed(const EnvState &st, hipStream_t s);
 hipError_t launch_mt_advance(const EnvState &st, int64_t words, hipStream_t s);
 
-// LSA, beta_hat and the selectors (asg_lsa.hip, asg_select.hip)
+// LSA, beta_hat and the selectors (asg_lsa.hip, asg_sap.hip, asg_select.hip)
 hipError_t launch_lsa_batched(const void *C, int dtype, const int64_t strides[3], int64_t B, int nr, int nc,
                               int maximize, int64_t *row_out, int64_t *col_out, int32_t *status_out,
                               hipStream_t s);

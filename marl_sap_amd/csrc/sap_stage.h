@@ -1,26 +1,43 @@
 // sap_stage.h -- the SequentialAssignmentProblemSelector of one env on one wave64 (sap_selectors.py:
 // 52-98, n <= m <= 64): its noisy Q column staged in registers (sap_stage), the certified fast path
 // (optionally warm-started) with the scipy-exact solver behind it, the actions out (sap_emit).
-// sap_select_kernel (asg_lsa.hip) runs one per wave; the same function called by the rollout
+// sap_select_kernel (asg_sap.hip) runs one per wave; the same function called by the rollout
 // kernel's Q-output waves after their env's Q rows measured slower.
+// Square SAP problems (n == m) first take the certified fast path (lsa_fast_reg64: column
+// reduction + shortest augmenting paths, used under a uniqueness certificate), the rest and
+// every uncertified problem the scipy-exact solver.
 #pragma once
 #include "asg_device.h"
+#include "lsa_reg64.h"
 #include "lsa_wave.h"
 
 namespace asg {
 
-// square SAP problems (n == m) first take the certified fast path (lsa_fast_reg64: column
-// reduction + shortest augmenting paths, used under a uniqueness certificate), the rest and
-// every uncertified problem the scipy-exact solver; -DASG_SAP_FAST=0: the exact solver only
-#ifndef ASG_SAP_FAST
-#define ASG_SAP_FAST 1
-#endif
-#ifndef ASG_SAP_PIN
-#define ASG_SAP_PIN 1
-#endif
-#ifndef ASG_SAP_PIN_BASE
-#define ASG_SAP_PIN_BASE 32
-#endif
+// rc's 64 rows += stdv z, z standard normal by Box-Muller (as torch.normal(mean, std) = mean +
+// std z) from the env's Philox key: counter (lane, i4, kKind, counter) gives rows 4 i4 .. 4 i4 + 3
+// of this lane's column (rows past the problem's are unused).  stdv by reference: by value,
+// sap_select_kernel's instances grow by 150-190 instructions and one of them starts to spill.
+template <uint32_t kKind, class RC>
+__device__ __forceinline__ void add_normal_noise(RC &rc, const float &stdv, const EnvKey &key, uint32_t counter) {
+    const int lane = threadIdx.x & (kWave - 1);
+    constexpr float k2m24 = 5.9604644775390625e-08f;  // 2^-24
+    constexpr float k2pi = 6.283185307179586f;
+#pragma unroll
+    for (int i4 = 0; i4 < 16; ++i4) {
+        const u32x4 r = philox4x32_10(u32x4{(uint32_t)lane, (uint32_t)i4, kKind, counter}, key.k0, key.k1);
+        const float u1a = (float)((r.x >> 8) + 1u) * k2m24, u2a = (float)(r.y >> 8) * k2m24;
+        const float u1b = (float)((r.z >> 8) + 1u) * k2m24, u2b = (float)(r.w >> 8) * k2m24;
+        const float ra = __builtin_sqrtf(-2.0f * __logf(u1a)), rb = __builtin_sqrtf(-2.0f * __logf(u1b));
+        const float z[4] = {ra * __cosf(k2pi * u2a), ra * __sinf(k2pi * u2a), rb * __cosf(k2pi * u2b),
+                            rb * __sinf(k2pi * u2b)};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = 4 * i4 + k;
+            if (i < 32) rc.lo[i] = rc.lo[i] + stdv * z[k];
+            else rc.hi[i - 32] = rc.hi[i - 32] + stdv * z[k];
+        }
+    }
+}
 
 // problem b's working column: Q column `lane` of env b plus its noise (std mean|Q| * eps * 2),
 // negated (maximize) -- ASG_E_LSA_INVALID (wave uniform) when the noisy matrix holds NaN or
@@ -63,26 +80,8 @@ __device__ __forceinline__ int sap_stage(const float *q, int64_t q0, int64_t q1,
     // random either way), stds = avg * eps * 2
     const float avg = wave_allreduce(asum, [](float x, float y) { return x + y; }) / (float)(n * m);
     const float stdv = avg * epsilon * 2.0f;
-    if (epsilon > 0.0f) {
-        const EnvKey key = env_key(seed, env_base + b);
-        constexpr float k2m24 = 5.9604644775390625e-08f;  // 2^-24
-        constexpr float k2pi = 6.283185307179586f;
-#pragma unroll
-        for (int i4 = 0; i4 < 16; ++i4) {  // rows 4*i4 .. 4*i4+3 of this column
-            const u32x4 r = philox4x32_10(u32x4{(uint32_t)lane, (uint32_t)i4, kCtrSapNoise, counter}, key.k0, key.k1);
-            const float u1a = (float)((r.x >> 8) + 1u) * k2m24, u2a = (float)(r.y >> 8) * k2m24;
-            const float u1b = (float)((r.z >> 8) + 1u) * k2m24, u2b = (float)(r.w >> 8) * k2m24;
-            const float ra = __builtin_sqrtf(-2.0f * __logf(u1a)), rb = __builtin_sqrtf(-2.0f * __logf(u1b));
-            const float z[4] = {ra * __cosf(k2pi * u2a), ra * __sinf(k2pi * u2a), rb * __cosf(k2pi * u2b),
-                                rb * __sinf(k2pi * u2b)};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = 4 * i4 + k;  // torch.normal(0, std) = 0 + std * z, then Q += noise
-                if (i < 32) rc.lo[i] = rc.lo[i] + stdv * z[k];
-                else rc.hi[i - 32] = rc.hi[i - 32] + stdv * z[k];
-            }
-        }
-    }
+    // torch.normal(0, std) = 0 + std * z, then Q += noise
+    if (epsilon > 0.0f) add_normal_noise<kCtrSapNoise>(rc, stdv, env_key(seed, env_base + b), counter);
     int bad = 0;
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
@@ -132,35 +131,23 @@ __device__ __forceinline__ void sap_select_one(const float *q, int64_t q0, int64
                                                float epsilon, uint64_t seed, uint32_t counter, int64_t env_base,
                                                int64_t b, float *col_out, int64_t *act_out, int32_t *status_out,
                                                int32_t *steps_out, double *duals, int warm, uint64_t *slot) {
-#if ASG_SAP_PIN
-    RegColPin<ASG_SAP_PIN_BASE> rc;  // the column in v[BASE .. BASE + 63]: one indexed move per row read
-#else
-    RegCostF32 rc;
-#endif
+    RegColPin rc;  // the column in v[32 .. 95]: one indexed move per row read
     int status = sap_stage<kDense64>(q, q0, q1, q2, n, m, epsilon, seed, counter, env_base, b, rc);
     int c4r[1] = {-1};
     int nsteps = 0, nfast = 0;
-#ifdef ASG_SAP_STAGE_ONLY  // timing experiments only: the staging and noise alone (wrong results)
-    float sum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) sum += rc.lo[k] + rc.hi[k];
-    if (__builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sum)) == 0x7fffffff) status = 1;
-    sap_emit<kCount>(b, status, (int)(threadIdx.x & 63), 0, n, m, col_out, act_out, status_out, steps_out);
-    return;
-#endif
     bool done = false;
     if constexpr (kWarm) {
         const int lane = threadIdx.x & 63;
         double *dp = duals + b * 64 + lane;
         const double vin = warm ? *dp : __builtin_nan("");
         double vnew = __builtin_nan("");
-        if (ASG_SAP_FAST && status == ASG_OK && n == m)
+        if (status == ASG_OK && n == m)
             done = lsa_fast_reg64<decltype(rc), kCount, true>(rc, n, c4r, &nfast, slot, vin, &vnew) == ASG_OK;
         // only certified duals carry over: an env whose fast path ended uncertified (ties, NaN)
         // or did not run stores NaN and starts cold next call (lsa_fast_reg64 fills vnew before
         // its certificate)
         *dp = done ? vnew : __builtin_nan("");
-    } else if (ASG_SAP_FAST && status == ASG_OK && n == m) {
+    } else if (status == ASG_OK && n == m) {
         done = lsa_fast_reg64<decltype(rc), kCount>(rc, n, c4r, &nfast, slot) == ASG_OK;
     }
     if (status == ASG_OK && !done) status = lsa_solve_reg64<decltype(rc), kCount>(rc, n, m, c4r, &nsteps);

@@ -52,6 +52,7 @@ def lib():
         L.ora_beta_hat.argtypes = [_dp, _i64p, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_double, _dp]
         L.ora_lsa.argtypes = [_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64p, _i64p]
         L.ora_lsa.restype = ctypes.c_int
+        L.ora_lsa_iterations.restype = ctypes.c_long
         L.ora_env_construct_reset.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 5 + \
             [_dp, _dp, _i64p, _dp, _dp]
         L.ora_env_construct_reset.restype = ctypes.c_int

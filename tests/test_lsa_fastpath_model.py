@@ -1,4 +1,4 @@
-"""Host model of the certified LSA fast path (csrc/lsa_wave.h lsa_fast_reg64, modelled in
+"""Host model of the certified LSA fast path (csrc/lsa_reg64.h lsa_fast_reg64, modelled in
 tools/lsa_fastpath_sim.py): column reduction + shortest augmenting paths from it, used only
 under the uniqueness certificate.  On CPU, against scipy itself:
   * whenever the certificate holds, the assignment is scipy's;

@@ -1,7 +1,9 @@
 #!/bin/bash
 # The certified SAP fast path: its parity tests, the SAP/LSA/HAA/runner parity tests, then the
-# bench's SAP leg against the exact-only library (build/lib_exact.so, -DASG_SAP_FAST=0):
-#   bash tools/gpu_sapfast.sh OUT_DIR
+# bench's SAP leg against the exact-only library build/lib_exact.so.  The ASG_SAP_FAST switch left
+# the sources after commit d559e7c, so that library is built from that commit (CPU side):
+#   bash tools/build_rev.sh d559e7c build/lib_exact.so -DASG_SAP_FAST=0
+# then on the GPU box: bash tools/gpu_sapfast.sh OUT_DIR
 set -o pipefail
 OUT=${1:-gpurun_out/sapfast}
 mkdir -p "$OUT"

@@ -5,8 +5,8 @@
 For SAP-selector matrices (Q of a random-init RNNAgent on the mock env's observations from
 the C oracle env, plus the selector's Gaussian noise of std 2 eps mean|Q|) and for uniform
 matrices, it counts the augmenting-path steps of
-  * scipy's algorithm (every row's Dijkstra from u = v = 0; csrc/lsa_wave.h lsa_solve_reg64),
-  * the certified fast path (csrc/lsa_wave.h lsa_fast_reg64): row + column reduction, then the
+  * scipy's algorithm (every row's Dijkstra from u = v = 0; csrc/lsa_reg64.h lsa_solve_reg64),
+  * the certified fast path (csrc/lsa_reg64.h lsa_fast_reg64): row + column reduction, then the
     same shortest-augmenting-path step for the rows it leaves free only,
 checks both assignments against scipy, and evaluates the fast path's uniqueness certificate
 (dual feasibility within S 2^-40, acyclic near-tight graph at S 2^-30).  --q-seq: the warm start
