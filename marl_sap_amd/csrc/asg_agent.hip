@@ -173,13 +173,14 @@ __device__ __forceinline__ void agent_rows(
     // ---- fc1: x^T = relu(W1 X^T + b1), X rows streamed from HBM, 2 chunks in flight ----
     f32x4 xB[4][kNT];
     {
-        f32x4 acc[4][kNT];  // start from the bias (C layout: unit 16 mt + 4 q + v)
+        // the bias is added once, after the products (C layout: unit 16 mt + 4 q + v): an
+        // accumulator that starts from it rounds at the bias's magnitude with every MFMA --
+        // with small weights or inputs several ulps of the result, where PyTorch has half of one
+        f32x4 acc[4][kNT];
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const float4 bb = *reinterpret_cast<const float4 *>(b1 + 16 * mt + 4 * q);
+        for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-            for (int nt = 0; nt < kNT; ++nt) acc[mt][nt] = f32x4{bb.x, bb.y, bb.z, bb.w};
-        }
+            for (int nt = 0; nt < kNT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
         const float *xr[kNT];
 #pragma unroll
         for (int nt = 0; nt < kNT; ++nt) xr[nt] = X + (ok[nt] ? rows[nt] : 0) * xs;
@@ -231,11 +232,13 @@ __device__ __forceinline__ void agent_rows(
             chunk(a4, w4);
         }
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
+        for (int mt = 0; mt < 4; ++mt) {
+            const float4 bb = *reinterpret_cast<const float4 *>(b1 + 16 * mt + 4 * q);
 #pragma unroll
             for (int nt = 0; nt < kNT; ++nt)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) xB[mt][nt][v] = fmaxf(acc[mt][nt][v], 0.f);
+                for (int v = 0; v < 4; ++v) xB[mt][nt][v] = fmaxf(acc[mt][nt][v] + comp(bb, v), 0.f);
+        }
     }
 
     // ---- recurrent layer -> h'^T in registers (hp[hb] = B operand of fc2's chunk hb) ----
@@ -331,7 +334,7 @@ __device__ __forceinline__ void agent_rows(
             const float4 bb = *reinterpret_cast<const float4 *>(bih + 16 * hb + 4 * q);
             f32x4 a2[kNT];
 #pragma unroll
-            for (int nt = 0; nt < kNT; ++nt) a2[nt] = f32x4{bb.x, bb.y, bb.z, bb.w};
+            for (int nt = 0; nt < kNT; ++nt) a2[nt] = f32x4{0.f, 0.f, 0.f, 0.f};  // bias last, as fc1
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const float4 w = Wihp[pk(t, hb, 4, lane)];
@@ -343,7 +346,7 @@ __device__ __forceinline__ void agent_rows(
 #pragma unroll
             for (int nt = 0; nt < kNT; ++nt)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) hp[hb][nt][v] = fmaxf(a2[nt][v], 0.f);
+                for (int v = 0; v < 4; ++v) hp[hb][nt][v] = fmaxf(a2[nt][v] + comp(bb, v), 0.f);
         }
         // h' block -> HBM (the new hidden state), one float4 per lane and row
 #pragma unroll
@@ -424,7 +427,7 @@ __device__ __forceinline__ void agent_rows(
         }
         f32x4 a2[kNT];
 #pragma unroll
-        for (int nt = 0; nt < kNT; ++nt) a2[nt] = f32x4{bq.x, bq.y, bq.z, bq.w};
+        for (int nt = 0; nt < kNT; ++nt) a2[nt] = f32x4{0.f, 0.f, 0.f, 0.f};  // bias last, as fc1
         float4 w2[4];
         if (w2l_on) {  // staged in LDS: ds_read, not a flat load through a merged pointer
             typedef const f32x4 __attribute__((address_space(3))) * lds_f4p;
@@ -446,6 +449,7 @@ __device__ __forceinline__ void agent_rows(
                 for (int nt = 0; nt < kNT; ++nt) a2[nt] = mfma4(comp(w2[t], e), hp[t][nt][e], a2[nt]);
 #pragma unroll
         for (int nt = 0; nt < kNT; ++nt) {
+            a2[nt] += f32x4{bq.x, bq.y, bq.z, bq.w};
             if (Q && ok[nt]) {
                 float *qp = Q + rows[nt] * nout + j0;
                 if (full && qvec) {

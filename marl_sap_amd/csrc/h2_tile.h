@@ -425,12 +425,20 @@ __device__ __forceinline__ void h2_tail(A &a, const u32x4v *Wl, const int (&sw)[
         if (h_zero) gru(std::true_type{});
         else gru(std::false_type{});
     } else {
-        // Linear + ReLU (use_rnn = False): h' = relu(W_rnn x + b_rnn), one gate of planes
+        // Linear + ReLU (use_rnn = False): h' = relu(W_rnn x + b_rnn), one gate of planes.  The
+        // bias is added once, after the products (as fc1 and fc2 do): an accumulator that starts
+        // from b 2^S rounds at the bias's magnitude with each of the six MFMAs, which with small
+        // weights is ~4 ulp of h' where PyTorch's fp32 has half of one.  The accumulators start
+        // from b * 0 with the zero in a register the compiler cannot see through: started from
+        // literal zeros, the GEN select and rollout instantiations came out 6e-5 off on rows
+        // 16..31, units 0..15 of every tile (hipcc of ROCm 7, gfx950; cause not found), and the
+        // bit-identity tests caught it.  Same instruction count as before.
         float scS[NT], un[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            scS[nt] = pow2f(Sg[nt]);
             un[nt] = pow2f(-Sg[nt]);
+            scS[nt] = 0.f;
+            asm volatile("" : "+v"(scS[nt]));
         }
 #pragma unroll
         for (int hb = 0; hb < 4; ++hb) {
@@ -447,7 +455,7 @@ __device__ __forceinline__ void h2_tail(A &a, const u32x4v *Wl, const int (&sw)[
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
-                for (int v = 0; v < 4; ++v) hp[hb][nt][v] = fmaxf(acc[nt][v] * un[nt], 0.f);
+                for (int v = 0; v < 4; ++v) hp[hb][nt][v] = fmaxf(__builtin_fmaf(acc[nt][v], un[nt], bb[v]), 0.f);
                 if (ok[nt] && (!HCOND || store_h))
                     *reinterpret_cast<float4 *>(a.Hout + rows[nt] * kHid + 16 * hb + 4 * q) =
                         make_float4(hp[hb][nt][0], hp[hb][nt][1], hp[hb][nt][2], hp[hb][nt][3]);

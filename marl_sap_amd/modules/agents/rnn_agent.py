@@ -318,7 +318,9 @@ class RNNFusedAgent(RNNAgent):
 
     def _packed(self, K, device):
         """Weights in the kernel's fragment order, re-packed only when a weight changed
-        (optimizer steps bump the tensors' version counters; load_state_dict too)."""
+        (optimizer steps bump the tensors' version counters; load_state_dict and in-place
+        no_grad updates too).  A write through `.data` bumps no counter: call
+        invalidate_pack() after one."""
         rnn = self.args.use_rnn
         ws = [self.fc1.weight, self.rnn.weight_ih if rnn else self.rnn.weight,
               self.rnn.weight_hh if rnn else None, self.fc2.weight]
@@ -333,6 +335,12 @@ class RNNFusedAgent(RNNAgent):
                                             self.n_out, int(bool(rnn)), p(buf), _lib.stream_ptr(device)))
             self._pack_buf, self._pack_key = buf, key
         return self._pack_buf
+
+    def invalidate_pack(self):
+        """Forget the packed weights: the next inference call packs them again.  Needed only
+        after a weight was written behind autograd's back (`w.data.mul_(..)`, a raw-pointer
+        copy), which leaves (data_ptr, _version) as they were."""
+        self._pack_key = None
 
 
 class FlatConstAgent(RNNAgent):

@@ -177,16 +177,24 @@ def test_select_draws_are_shard_invariant(fused):
     assert 0.2 < frac < 0.6, frac  # about eps * (1 - 1/available) of the rows explore off the argmax
 
 
-@pytest.mark.parametrize("use_rnn", [True])
-def test_split_bf16_gru_is_fp32_accurate(use_rnn):
-    """The GRU's products run on three-way-split bf16 MFMAs (asg_rnn_agent_mfma_mode bit 0):
-    against a float64 evaluation of the same module, the fused kernel's error is of the
-    same size as PyTorch's own fp32 error (not bf16's ~4e-3), for h' and Q."""
+@pytest.mark.parametrize("K,m", [(256, 64), (132, 300)])
+def test_split_gru_is_fp32_accurate(K, m):
+    """The GRU agent against a float64 evaluation of the same module: the fused kernel's error is
+    of the size of PyTorch's own fp32 error, for h' and Q.  (256, 64) runs the split-f16 kernel
+    (asg_rnn_agent_mode 4: every layer's products on two-way-split f16 MFMAs, not f16's ~5e-4);
+    (132, 300) -- n_out > 256 -- runs the f32-MFMA kernel whose GRU products are three-way-split
+    bf16 (asg_rnn_agent_mfma_mode bit 0; not bf16's ~4e-3).  The second is held to the project's
+    rule with the gate floor G = 18 * 2^-24 of tests/agent_scale_cases.py (the gates' rcp / exp2
+    formula is accurate in absolute terms): G on h', G max_j sum_k |W2[j, k]| on Q."""
     from marl_sap_amd import _lib
-    assert _lib.lib().asg_rnn_agent_mfma_mode() & 1
+    from tests.agent_scale_cases import GATE_FLOOR
+    L = _lib.lib()
+    assert L.asg_rnn_agent_mfma_mode() & 1
+    mode = L.asg_rnn_agent_mode(K, 64, m, 1)
+    assert mode == (4 if m <= 256 else L.asg_rnn_agent_mfma_mode())
     torch.manual_seed(11)
-    R, m, K = 64 * 128, 64, 256
-    args = SimpleNamespace(hidden_dim=64, use_rnn=use_rnn, m=m)
+    R = 64 * 128
+    args = SimpleNamespace(hidden_dim=64, use_rnn=True, m=m)
     ref = RNNAgent(K, args).to(DEV)
     fused = RNNFusedAgent(K, args).to(DEV)
     fused.load_state_dict(ref.state_dict())
@@ -198,9 +206,13 @@ def test_split_bf16_gru_is_fp32_accurate(use_rnn):
         q64, h64 = ref64(x.double(), h.double())
         q32, h32 = ref(x, h)
         qf, hf = fused(x, h)
-    for got, want, base in ((hf, h64, h32), (qf, q64, q32)):
+    w2 = ref.fc2.weight.double().abs().sum(1).max().item()
+    for got, want, base, floor in ((hf, h64, h32, GATE_FLOOR), (qf, q64, q32, GATE_FLOOR * w2)):
         err_fused = (got.double() - want).abs().max().item()
         err_torch = (base.double() - want).abs().max().item()
-        print(f"max |err| vs float64: fused {err_fused:.3e}, torch fp32 {err_torch:.3e}")
-        assert err_fused <= 4 * err_torch + 1e-7, (err_fused, err_torch)
+        print(f"mode {mode} max |err| vs float64: fused {err_fused:.3e}, torch fp32 {err_torch:.3e}")
+        if mode == 4:
+            assert err_fused <= 4 * err_torch + 1e-7, (err_fused, err_torch)
+        else:
+            assert err_fused <= 4 * err_torch + 1e-7 * want.abs().max().item() + floor, (err_fused, err_torch)
         assert err_fused < 1e-5

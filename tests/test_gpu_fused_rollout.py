@@ -27,18 +27,50 @@ class _Logger:
         pass
 
 
-def _injected_table(n, m, T, seed=0):
-    """a sat_prox_mat-shaped [n, m, T] float64 table: sparse bumps plus exact zeros"""
-    r = np.random.RandomState(seed)
+def _injected_table(n, m, T, seed=None, large=False):
+    """a sat_prox_mat-shaped [n, m, T] float64 table: sparse bumps plus exact zeros.  large: two
+    tasks x 40, two x 5000 (the others x 1) and a per-agent multiplier from {1, 1, 30}, zeros kept
+    -- observation rows from below 16 (fc1's first input scale holds) to 1.5e6 (fc1 re-runs at the
+    row's own scale) inside one 32-agent tile."""
+    # the large table's seed: one at which tile 0 of every shape used here mixes both kinds of rows
+    r = np.random.RandomState((5 if large else 0) if seed is None else seed)
     t = r.rand(n, m, T) * (r.rand(n, m, 1) > 0.6) * r.choice([1.0, 10.0], size=(1, m, 1))
+    if large:
+        task = np.ones(m)
+        task[r.permutation(m)[:4]] = [40.0, 40.0, 5000.0, 5000.0]
+        t = t * task[None, :, None] * r.choice([1.0, 1.0, 30.0], size=(n, 1, 1))
     return t
+
+
+def _lookahead(table, T, L):
+    """the obs lookahead blocks of every batch row, [T + 1, n, L * m] float32: row t holds
+    table[:, :, t + l] for l < L, zero past T (mock_constellation_env.py:107-112, :147-152)"""
+    n, m, _ = table.shape
+    out = np.zeros((T + 1, n, L, m), dtype=np.float32)
+    for t in range(T + 1):
+        for l in range(min(L, T - t)):
+            out[t, :, l, :] = table[:, :, t + l].astype(np.float32)
+    return out.reshape(T + 1, n, L * m)
+
+
+def _check_large(obs, n, m, T, L):
+    """obs [E, T + 1, n, m (L + 1)] of an injected_large run: fc1's retry really ran, in a tile
+    that also holds rows which do not retry, and the rows are the first attempt's (stored once):
+    exactly float32(table)."""
+    look = obs[..., m:].numpy()
+    assert look.max() >= 16.0
+    rowmax = look[0, 0, :32].max(-1)
+    assert (rowmax >= 16.0).any() and (rowmax < 16.0).any() and (rowmax > 0).all()
+    want = _lookahead(_injected_table(n, m, T, large=True), T, L)
+    assert np.array_equal(look, np.broadcast_to(want, look.shape))
 
 
 def _rollout(n, m, T, L, E, eps, benefits, fused, episodes=2, quirks=(), protocol="episode", seed=7, use_rnn=True,
              mac="basic_mac", rng="philox", **extra):
     env_args = dict(n=n, m=m, T=T, L=L, lambda_=0.5, bids_as_actions=False, seed=seed, benefits=benefits)
-    if benefits == "injected":
-        env_args["sat_prox_mat"] = _injected_table(n, m, T)
+    if benefits in ("injected", "injected_large"):
+        env_args["sat_prox_mat"] = _injected_table(n, m, T, large=benefits == "injected_large")
+        env_args["benefits"] = "injected"
     args = SimpleNamespace(
         batch_size_run=E, env="mock_constellation_env", env_args=env_args,
         env_rng=rng, env_quirks=tuple(quirks), runner_protocol=protocol, test_nepisode=1,
@@ -99,6 +131,13 @@ def test_fused_rollout_is_bit_identical(n, m, T, L, E, eps, benefits, use_rnn):
     (20, 25, 5, 3, 9, 0.2, "bump", "mt19937", False),      # the reference's default env, Linear agent
     (64, 64, 5, 3, 10, 0.1, "injected", "philox", True),   # sat_prox_mat= (one table for every env)
     (33, 41, 4, 2, 6, 0.3, "injected", "mt19937", False),  # odd m, injected table, MT19937 permutations
+    # injected_large: fc1's retry inside the rollout tiles (some rows of a tile at the first scale,
+    # some re-run at their own; the rows stored once, from the first attempt)
+    (64, 64, 5, 3, 10, 0.1, "injected_large", "philox", True),    # the wave-pair instances
+    (64, 64, 5, 3, 10, 0.1, "injected_large", "philox", False),
+    (20, 25, 5, 3, 9, 0.2, "injected_large", "philox", True),     # the ragged (GEN) tile
+    (33, 41, 4, 2, 6, 0.3, "injected_large", "mt19937", False),   # odd m, MT19937 permutations
+    (32, 256, 4, 3, 5, 0.1, "injected_large", "philox", True),    # fc1 slices through L2, the late store order
 ])
 def test_fused_rollout_table_modes_bit_identical(n, m, T, L, E, eps, benefits, rng, use_rnn):
     """The episode kernel on the handle's float64 table (MT19937 compat tables, injected
@@ -106,7 +145,11 @@ def test_fused_rollout_table_modes_bit_identical(n, m, T, L, E, eps, benefits, r
     separate launches.  Reference: mock_constellation_env.py:22,32-37 (sat_prox_mat=), :94-114."""
     b = _rollout(n, m, T, L, E, eps, benefits, fused=False, use_rnn=use_rnn, rng=rng)
     for mode in ("always", "step"):
-        _same(*_rollout(n, m, T, L, E, eps, benefits, fused=mode, use_rnn=use_rnn, rng=rng), *b)
+        a = _rollout(n, m, T, L, E, eps, benefits, fused=mode, use_rnn=use_rnn, rng=rng)
+        _same(*a, *b)
+        if benefits == "injected_large":
+            for fields, _, _ in a[0]:
+                _check_large(fields["obs"], n, m, T, L)
 
 
 def test_fused_rollout_quirks_and_parallel_protocol():

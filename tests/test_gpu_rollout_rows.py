@@ -48,9 +48,33 @@ def _is_poison(v):
     return bool((_raw(v) == POISON).all())
 
 
-def _table(n, m, T, seed=0):
-    r = np.random.RandomState(seed)
-    return r.rand(n, m, T) * (r.rand(n, m, 1) > 0.6) * r.choice([1.0, 10.0], size=(1, m, 1))
+def _table(n, m, T, seed=None, large=False):
+    """large: two tasks x 40, two x 5000 and a per-agent multiplier from {1, 1, 30} (zeros kept):
+    observation rows below 16 and up to 1.5e6 in one 32-agent tile -- fc1's retry"""
+    # the large table's seed: one at which tile 0 of every shape used here mixes both kinds of rows
+    r = np.random.RandomState((5 if large else 0) if seed is None else seed)
+    t = r.rand(n, m, T) * (r.rand(n, m, 1) > 0.6) * r.choice([1.0, 10.0], size=(1, m, 1))
+    if large:
+        task = np.ones(m)
+        task[r.permutation(m)[:4]] = [40.0, 40.0, 5000.0, 5000.0]
+        t = t * task[None, :, None] * r.choice([1.0, 1.0, 30.0], size=(n, 1, 1))
+    return t
+
+
+def _check_large(obs_bytes, n, m, T, L):
+    """the raw obs field [E, T + 1, n, 4 m (L + 1)] of an injected_large run: the retry ran next to
+    rows that keep the first scale, and the lookahead blocks are float32(table) -- stored once,
+    from the first attempt"""
+    look = obs_bytes.view(torch.float32)[..., m:].numpy()
+    assert look.max() >= 16.0
+    rowmax = look[0, 0, :32].max(-1)
+    assert (rowmax >= 16.0).any() and (rowmax < 16.0).any()
+    table = _table(n, m, T, large=True)
+    want = np.zeros((T + 1, n, L, m), dtype=np.float32)
+    for t in range(T + 1):
+        for l in range(min(L, T - t)):
+            want[t, :, l, :] = table[:, :, t + l].astype(np.float32)
+    assert np.array_equal(look, np.broadcast_to(want.reshape(T + 1, n, L * m), look.shape))
 
 
 def _episodes(n, m, T, L, E, fused, use_rnn=True, benefits="bump", rng="philox", selector="epsilon_greedy",
@@ -58,8 +82,9 @@ def _episodes(n, m, T, L, E, fused, use_rnn=True, benefits="bump", rng="philox",
     """`episodes` episodes of the runner on one poisoned, reused batch: per episode the fields'
     bytes, the returns and the hidden state.  selector "sap": the Q-output schedule (step_q)."""
     env_args = dict(n=n, m=m, T=T, L=L, lambda_=0.5, bids_as_actions=False, seed=7, benefits=benefits)
-    if benefits == "injected":
-        env_args["sat_prox_mat"] = _table(n, m, T)
+    if benefits in ("injected", "injected_large"):
+        env_args["sat_prox_mat"] = _table(n, m, T, large=benefits == "injected_large")
+        env_args["benefits"] = "injected"
     sap = selector == "sap"
     args = SimpleNamespace(
         batch_size_run=E, env="mock_constellation_env", env_args=env_args, env_rng=rng, env_quirks=(),
@@ -134,6 +159,21 @@ def test_poisoned_episodes_other_64x64_instances(benefits, rng, selector):
         fused = _episodes(fused=mode, **kw)
         _same(fused, split)
         assert all(ep[3] for ep in fused), mode
+
+
+@pytest.mark.parametrize("selector", ["epsilon_greedy", "sap"])
+def test_poisoned_episodes_large_table_three_envs(selector):
+    """The injected table with rows from below 16 to 1.5e6 (fc1 re-runs for part of each tile), three
+    envs, on the poisoned batch: epsilon-greedy and the Q-output schedule."""
+    kw = dict(n=64, m=64, T=4, L=3, E=3, benefits="injected_large", selector=selector)
+    split = _episodes(fused=False, **kw)
+    assert all(ep[3] for ep in split)
+    for mode in ((True,) if selector == "sap" else ("always", "step")):
+        fused = _episodes(fused=mode, **kw)
+        _same(fused, split)
+        assert all(ep[3] for ep in fused), mode
+        for ep in fused:
+            _check_large(ep[0]["obs"], 64, 64, 4, 3)
 
 
 def test_poisoned_chunk_inside_an_episode():
