@@ -588,6 +588,11 @@ int asg_bids_select_count(asg_handle *h, const float *q, const int64_t q_strides
  * agent's. */
 int asg_rollout_l2_slices(int n, int m, int L, int use_rnn);
 int asg_step_select_l2_slices(int n, int m, int L);
+/* Steps per group G of the rollout kernel's wave-pair mapping (n = m = 64, launches with two
+ * or more agent passes): a group's env transitions run together after its G agent passes.  G is
+ * what the LDS behind the resident fc1 slices holds of the pair's task history (GRU, L = 3: 6);
+ * 0 when the pair mapping does not take the shape. */
+int asg_rollout_defer_steps(int n, int m, int L, int use_rnn);
 
 /* ==== RealConstellationEnv ======================================
  * Batched form of src/envs/real_constellation_env.py with injected benefits

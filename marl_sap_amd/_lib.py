@@ -42,7 +42,7 @@ EXPORTS = ["asg_abi_version", "asg_last_error", "asg_create", "asg_destroy", "as
            "asg_real_get_returns", "asg_real_get_step", "asg_real_obs_size", "asg_filtered_topm",
            "asg_filtered_benefits", "asg_filtered_epsilon_greedy", "asg_filtered_soft_map", "asg_real_haal_select",
            "asg_real_haal_num_sequences", "asg_step_select", "asg_step_select_l2_slices", "asg_rollout",
-           "asg_rollout_l2_slices", "asg_reset_rollout", "asg_sap_select_into", "asg_step_forward",
+           "asg_rollout_l2_slices", "asg_rollout_defer_steps", "asg_reset_rollout", "asg_sap_select_into", "asg_step_forward",
            "asg_sap_noise", "asg_random_rollout", "asg_sap_select_warm", "asg_bids_select",
            "asg_reset_forward", "asg_step_ex", "asg_step_forward_ex", "asg_bids_select_count",
            "asg_rnn_agent_unroll", "asg_rnn_agent_unroll_backward", "asg_mlp_agent_unroll",
@@ -178,6 +178,8 @@ def lib():
         L.asg_rollout.argtypes = [vp, ctypes.POINTER(AsgBatchView), i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                   i32, vp, i64, vp, dbl, u64, u64, vp, vp]
         L.asg_rollout_l2_slices.argtypes = [i32, i32, i32, i32]
+        if hasattr(L, "asg_rollout_defer_steps"):  # absent from older A/B builds
+            L.asg_rollout_defer_steps.argtypes = [i32, i32, i32, i32]
         L.asg_reset_rollout.argtypes = [vp, ctypes.POINTER(AsgBatchView), i32, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                         i32, vp, i64, vp, dbl, u64, u64, vp, vp]
         L.asg_sap_select_into.argtypes = [vp, i64p, i64, i32, i32, dbl, u64, u64, i64, vp, vp, vp, vp]

@@ -648,6 +648,7 @@ static void *tm_base(const asg_field &f, int64_t E, int64_t d2, int64_t d3, int6
 
 int asg_step_select_l2_slices(int n, int m, int L) { return asg::rollout_l2_slices(n, m, L, 1); }
 int asg_rollout_l2_slices(int n, int m, int L, int use_rnn) { return asg::rollout_l2_slices(n, m, L, use_rnn); }
+int asg_rollout_defer_steps(int n, int m, int L, int use_rnn) { return asg::rollout_defer_steps(n, m, L, use_rnn); }
 
 // asg_rollout and asg_reset_rollout (reset: the envs' reset runs in the same launch, before
 // the selection on row ts)

@@ -195,6 +195,22 @@ int rollout_l2_slices(int n, int m, int L, int use_rnn) {
     return h2_lds_plan(g, use_rnn != 0, g.Pp / 32, scr).l2_slices;
 }
 
+// The pair mapping's group size G (steps whose transitions are deferred together): what the
+// LDS behind the plan's fc1 slices holds per wave pair (pair_scratch_bytes), the plan itself
+// left as it is -- a resident fc1 slice is worth more than a longer group.  0: not a shape of
+// the pair mapping.
+int rollout_defer_steps(int n, int m, int L, int use_rnn) {
+    if (n != 64 || m != 64 || !rollout_shape_ok(n, m, L, m * (L + 1))) return 0;
+    const H2Geom g = h2_geom(m * (L + 1), m);
+    const int64_t scr = ((int64_t)rollout_scratch_bytes(n, m) * kH2Waves + 15) / 16;
+    const H2Lds plan = h2_lds_plan(g, use_rnn != 0, g.Pp / 32, scr);
+    if (!plan.w2l) return 0;
+    const int64_t room = (kH2LdsBytes - plan.scratch_off * 16) / (kH2Waves / 2);  // bytes per pair
+    int G = kMaxDeferSteps;
+    while (G > 0 && pair_scratch_bytes(G) > room) --G;
+    return G;
+}
+
 hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, int k0, int steps, int select_first,
                           int select_last, int reset, const float4 *packed, const float *b1, const float *bi, const float *bh,
                           const float *b2, int use_rnn, const float *Hin, int64_t hs, float *Hout, float *Q, float epsilon,
@@ -287,6 +303,13 @@ hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, in
         passes += kk < st.T && (kk < ra.k1 || select_last);
     }
     lc.pair = lc.sq64 && !Q && passes >= 2;
+    if (lc.pair) {
+        // the pairs' scratch takes the wave slots' place, and the room behind them for the task history
+        ra.defer = rollout_defer_steps(st.n, st.m, st.L, use_rnn);
+        if (ra.defer < 1) return hipErrorInvalidValue;
+        const int64_t pair_f4 = (int64_t)pair_scratch_bytes(ra.defer) * (kH2Waves / 2) / 16;
+        if (pair_f4 > scr_f4) lc.lds = (size_t)(plan.scratch_off + pair_f4) * 16;
+    }
     // envs in flight per workgroup: one per wave, or one per wave pair, whose scratch is the
     // pair's two wave slots of the plan above
     const int per_wg = lc.pair ? kH2Waves / 2 : kH2Waves;

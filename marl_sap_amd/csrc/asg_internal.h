@@ -170,6 +170,7 @@ struct RolloutSlabs {
 };
 bool rollout_shape_ok(int n, int m, int L, int K);
 int rollout_l2_slices(int n, int m, int L, int use_rnn);
+int rollout_defer_steps(int n, int m, int L, int use_rnn);
 hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, int k0, int steps, int select_first,
                           int select_last, int reset, const float4 *packed, const float *b1, const float *bi, const float *bh,
                           const float *b2, int use_rnn, const float *Hin, int64_t hs, float *Hout, float *Q,

@@ -807,8 +807,9 @@ struct H2Lds {
     int64_t scratch_off;  // u32x4v units
     size_t bytes;
 };
+constexpr int64_t kH2LdsBytes = 160 * 1024;
 static inline H2Lds h2_lds_plan(const H2Geom &g, bool rnn, int s0, int64_t reserve_f4) {
-    constexpr int64_t kCap = 160 * 1024 / 16;
+    constexpr int64_t kCap = kH2LdsBytes / 16;
     H2Lds p{};
     p.w2l = lds_w2_off(rnn, g.nct) + w2s_f4(g.nct) + reserve_f4 <= kCap;
     const int64_t w1off = lds_w1_off(rnn, g.nct, p.w2l);

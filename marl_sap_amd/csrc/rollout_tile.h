@@ -72,7 +72,8 @@ struct RolloutArgs {
     float epsilon;
     uint32_t sk0, sk1, counter;
     int *sel_err;
-    int64_t scratch_off;  // per-wave LDS scratch (u32x4v units; a wave pair's = its two waves' slots)
+    int64_t scratch_off;  // LDS scratch (u32x4v units): a slot per wave, or pair_scratch_bytes(defer) per wave pair
+    int defer;            // the pair mapping: steps per group of deferred transitions (G >= 1)
     // bids_as_actions (asg_step_forward): the tasks of transition k0 are the handle's LSA
     // assignments of the bids row [E][n] instead of the batch's actions row
     const int *assign;
@@ -169,8 +170,11 @@ __device__ __forceinline__ void rollout_actions_from_batch(RA &ra, int64_t e, in
 
 // one transition (mock_constellation_env.py:116-162 + the runner's rows): rewards, returns,
 // terminated / filled / prev_assigns rows; the tasks come from the LDS (selected in this
-// launch, or read from the batch by the env prologue)
-template <int TAB, int SQ, class RA>
+// launch, or read from the batch by the env prologue).  DEFER (the wave-pair mapping, which runs
+// a group's transitions after its tiles): the previous tasks are only read (the row of the task
+// history before the step's) and the step's reward sum goes to *s_ret as it is; the caller
+// folds the sums into the return in step order
+template <int TAB, int SQ, bool DEFER = false, class RA>
 __device__ __forceinline__ void rollout_transition(RA &ra, int64_t e, int k, int ts, const EnvKey &key,
                                                    const uint64_t *s_scl, int *s_cnt, uint16_t *s_act,
                                                    uint16_t *s_prev, double *s_ret) {
@@ -213,7 +217,7 @@ __device__ __forceinline__ void rollout_transition(RA &ra, int64_t e, int k, int
                 const double bh = beta - ra.lambda_ * pen;
                 rr = bh > 0.0 ? bh / (double)s_cnt[j] : bh;
                 if (ra.rew) ra.rew[((int64_t)ts * ra.E + e) * n + i] = (float)rr;
-                s_prev[i] = (uint16_t)j;
+                if (!DEFER) s_prev[i] = (uint16_t)j;
                 if (ra.prevb)
                     ra.prevb[((int64_t)(ts + 1) * ra.E + e) * n + i] =
                         (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : j;
@@ -227,7 +231,9 @@ __device__ __forceinline__ void rollout_transition(RA &ra, int64_t e, int k, int
     if (ra.T_trans) rewards(std::true_type{});
     else rewards(std::false_type{});
     if (lane == 0) {
-        *s_ret += sum;  // the return lives in LDS: a register copy spilled, its reload drained the stores
+        // the return lives in LDS: a register copy spilled, its reload drained the stores
+        if (DEFER) *s_ret = sum;
+        else *s_ret += sum;
         bool term = k + 1 >= ra.T;  // terminated = done != info.get("T", False)
         if (ra.quirks & ASG_QUIRK_PARALLEL_TERMINATED) term = (e != 0);
         if (ra.term) ra.term[(int64_t)ts * ra.E + e] = term;
@@ -917,35 +923,50 @@ __device__ __forceinline__ void pair_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// pair scratch (bytes): task-scale bits, one u64 per wave at 32 sub | the env's return f64 at
-// 64 | collision counts [64] int at 80 | tasks [2][64] u16 at 336 (parity double buffer) |
-// previous tasks [64] u16 at 592.  It lives in the two waves' scratch slots of the LDS plan.
-constexpr int kPairScratchBytes = 720;
-static_assert(kPairScratchBytes <= 2 * rollout_scratch_bytes(64, 64), "pair scratch: two wave slots");
+// pair scratch (bytes), G = steps per group of deferred transitions: task-scale bits, one u64
+// per wave at 8 sub | the env's return f64 at 16 | collision counts [64] int per wave at
+// 32 + 256 sub | previous tasks [64] u16 at 544 | from 672 the task history, G + 1 rows of
+// 136 bytes: the step's tasks [64] u16, then its reward sum f64 (none in the last row).  Every
+// offset is a constant: nothing but the pair's base depends on G.  The launch sizes G to the LDS
+// the fc1 slices leave (rollout_defer_steps).
+constexpr int kPairHistOff = 672;
+constexpr int kPairRow = 68;        // history row stride (u16 units)
+constexpr int kMaxDeferSteps = 16;  // with room to spare (Linear agent, L = 1): a T = 20 episode in two groups
+__host__ __device__ constexpr int pair_scratch_bytes(int G) {
+    return (kPairHistOff + 2 * kPairRow * G + 128 + 15) / 16 * 16;
+}
 
 // A wave pair per env, n = m = 64 (the SQ64 instances): waves 2 p and 2 p + 1 of the workgroup
 // are pair p, which takes envs 4 b + p, + 4 gridDim.x, ...; wave `sub` of the pair runs tile
 // `sub` of its env in every pass, so its next agent tile is the same 32 agents one step later
 // and the hidden state stays in its registers between passes (hN <- h' after the recurrent
-// layer): Hin is read by the launch's first agent pass, Hout written by its last.  One wave of
-// the pair (trw; on another SIMD from pair to pair) also runs the transitions, lane = agent, and
-// owns the env's return, counts and previous tasks.  The pair shares the tasks: the selection
-// of pass p writes buffer (p + 1) & 1, each wave its own 32 entries; the transition and the
-// tiles after it read all / their own 32 of that buffer once the step's barrier has passed.
-// A buffer is rewritten two barriers after it was filled and its readers lie between them, so
-// one barrier per step is enough.
+// layer): Hin is read by the launch's first agent pass, Hout written by its last.
+// Nothing in a step's tiles reads what the step's transition produces, and a tile reads only
+// its own 32 of the selected tasks, which its wave wrote: so the steps run in groups of G.
+// Within a group a wave runs its tiles back to back with no barrier; the selection of the
+// group's j-th step writes row j + 1 of the pair's task history (each wave its own 32 entries)
+// and the wave's next tile reads its own 32 of that row.  At the group's end, behind one
+// barrier, the two waves share out the group's transitions (the steps of each wave's parity,
+// lane = agent, each wave its own counts): step j's tasks are row j, its previous tasks row
+// j - 1 (s_prev for the group's first), its float64 reward sum goes to row j's tail.  Behind a
+// second barrier one lane folds the sums into the env's return in step order -- the additions
+// of the per-step code -- and each wave carries its 32 entries of the group's last rows over
+// (row G -> row 0, the last step's tasks -> s_prev, or the env's state after the last group).
+// Two barriers per group and one per env for the prologue; every wave of the workgroup executes
+// the same number of them (see pair_barrier).
 template <bool RNN, bool W2L, int TAB, bool QOUT>
 __device__ __forceinline__ void rollout_envs_pair(const RolloutArgs &ra, u32x4v *s_h2, const int (&sw)[4]) {
     constexpr int SQ = 64, n = 64, m = 64;
-    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pr = wv >> 1, sub = wv & 1;
-    const bool trw = sub == (pr >> 1);
-    char *scr = reinterpret_cast<char *>(s_h2 + ra.scratch_off) + pr * (2 * rollout_scratch_bytes(n, m));
-    uint64_t *s_scl = reinterpret_cast<uint64_t *>(scr + 32 * sub);
-    double *s_ret = reinterpret_cast<double *>(scr + 64);
-    int *s_cnt = reinterpret_cast<int *>(scr + 80);
-    uint16_t *s_act2 = reinterpret_cast<uint16_t *>(scr + 336);
-    uint16_t *s_prev = reinterpret_cast<uint16_t *>(scr + 592);
+    const bool trw = sub == (pr >> 1);  // the prologue's and the return's wave (on another SIMD from pair to pair)
+    char *scr = reinterpret_cast<char *>(s_h2 + ra.scratch_off) + pr * pair_scratch_bytes(ra.defer);
+    uint64_t *s_scl = reinterpret_cast<uint64_t *>(scr + 8 * sub);
+    double *s_ret = reinterpret_cast<double *>(scr + 16);
+    int *s_cnt = reinterpret_cast<int *>(scr + 32 + 256 * sub);
+    uint16_t *s_prev = reinterpret_cast<uint16_t *>(scr + 544);
+    uint16_t *s_hist = reinterpret_cast<uint16_t *>(scr + kPairHistOff);
+    auto s_sum = [&](int j) { return reinterpret_cast<double *>(s_hist + kPairRow * j + 64); };
     constexpr int kPairs = kH2Waves / 2;
     const int64_t GP = (int64_t)gridDim.x * kPairs;
     // the loop bound is the workgroup's: a pair past E skips the work and takes the barriers
@@ -954,6 +975,10 @@ __device__ __forceinline__ void rollout_envs_pair(const RolloutArgs &ra, u32x4v 
         asm volatile("" : "+s"(e));
         const bool active = e < ra.E;
         const EnvKey key = env_key(ra.seed, ra.env_base + e);
+        // the lane index anew for the prologue (and below for the group's end): per-lane addresses
+        // formed from a kernel-wide one were hoisted out of the env loop and spilled
+        int lane = threadIdx.x & 63;
+        asm volatile("" : "+v"(lane));
         if (active) {
             // task scales as bits (Philox mode): each wave its own copy
             if (!TAB) {
@@ -989,56 +1014,102 @@ __device__ __forceinline__ void rollout_envs_pair(const RolloutArgs &ra, u32x4v 
                         ra.prevb[((int64_t)ra.ts0 * ra.E + e) * n + lane] = (ra.quirks & ASG_QUIRK_PREV_ASSIGNS_ZERO) ? 0 : p;
                     if (TAB && ra.reset && lane == 0 && ra.filled) ra.filled[(int64_t)ra.ts0 * ra.E + e] = 1;
                 }
-                s_act2[lane] = 0;
+                s_hist[lane] = 0;
                 if (lane == 0) *s_ret = ra.reset ? 0.0 : ra.returns[e];
-                if (!ra.select_first) rollout_actions_from_batch(ra, e, ra.ts0, s_act2);
+                if (!ra.select_first) rollout_actions_from_batch(ra, e, ra.ts0, s_hist);
             }
         }
         wave_lds_fence();
-        pair_barrier();  // the batch's tasks (buffer 0) reach the other wave
+        pair_barrier();  // the batch's tasks (row 0) and the previous tasks reach the other wave
         KRolloutArgs *const kra = (KRolloutArgs *)__builtin_amdgcn_kernarg_segment_ptr();
         const int sf = ra.select_first ? 1 : 0;
         const int nit = ra.k1 - ra.k0 + sf;
-        int pass = 0;
         f32x4 hN[4][kH2NT];  // the wave's h_t rows: loaded by pass 0, h' of the pass before after it
         auto has_agent = [&](auto &rr, int it) {
             const int kk = rr.k0 + it - sf + 1;
             return it < nit && kk < rr.T && (kk < rr.k1 || rr.select_last);
         };
-        for (int it = 0; it < nit; ++it) {
-            auto &ri = rollout_args(kra);
-            const int k = ri.k0 + it - sf;
-            const int ts = ri.ts0 + (k - ri.k0);
-            const bool first_sel = it < sf;
-            const bool agent = has_agent(ri, it);
-            uint16_t *const sa = s_act2 + n * (pass & 1), *const saw = s_act2 + n * ((pass & 1) ^ 1);
+        // groups of G steps: the tiles of each step, then the group's transitions.  Every trip
+        // count below is launch-uniform (nit, G), so each wave of the workgroup meets the same
+        // barriers
+        for (int g0 = 0; g0 < nit; g0 += rollout_args(kra).defer) {
+            const int gn = min(rollout_args(kra).defer, nit - g0);
+            // a pass's index is its step's: only the launch's last step can lack an agent pass
+            for (int j = 0; j < gn; ++j) {
+                const int it = g0 + j, pass = it;
+                auto &ri = rollout_args(kra);
+                const int k = ri.k0 + it - sf;
+                const int ts = ri.ts0 + (k - ri.k0);
+                const bool first_sel = it < sf;
+                const bool agent = has_agent(ri, it);
+                // the step's tasks: row j of the history; its selection writes row j + 1
+                uint16_t *const sa = s_hist + kPairRow * j, *const saw = sa + kPairRow;
+                if (active) {
+                    const int kk = k + 1;
+                    if (agent) {
+                        // the launch's last agent pass stores h' (a scalar: as a bool it went through
+                        // a byte of scratch, reloaded behind the tile's stores)
+                        const int last = __builtin_amdgcn_readfirstlane(has_agent(ri, it + 1) ? 0 : 1);
+                        rollout_tile<RNN, W2L, false, TAB, QOUT, true, SQ>(rollout_args(kra), e, sub, kk, ts + 1,
+                                                                           !first_sel || ri.reset, !first_sel, pass, key,
+                                                                           s_scl, sa, saw, s_h2, sw, hN, pass > 0,
+                                                                           HKeep{last});
+                    } else {
+                        rollout_tile<RNN, W2L, false, TAB, QOUT, false, SQ>(rollout_args(kra), e, sub, kk, ts + 1, true, true,
+                                                                            0, key, s_scl, sa, saw, s_h2, sw, hN, false,
+                                                                            HKeep{0});
+                    }
+                }
+                wave_lds_fence();
+            }
+            pair_barrier();  // the group's tasks (rows 0 .. gn) reach both waves' transitions
+            // the wave's 32 entries of what the next group (or the env's state) takes over: the
+            // previous tasks after the group's last step, and the tasks its last selection chose.
+            // Read before the second barrier, written after it: between the two barriers the
+            // rows and s_prev are read-only
+            int lane = threadIdx.x & 63;
+            asm volatile("" : "+v"(lane));
+            const int own = 32 * sub + (lane & 31);
+            const bool moved = g0 + gn > sf;  // the group's last step has a transition
+            uint16_t t_last = 0, t_next = 0;
             if (active) {
-                if (trw && !first_sel && !(ASG_ROLLOUT_XSKIP & 256))
-                    rollout_transition<TAB, SQ>(rollout_args(kra), e, k, ts, key, s_scl, s_cnt, sa, s_prev, s_ret);
-                const int kk = k + 1;
-                if (agent) {
-                    // the launch's last agent pass stores h' (a scalar: as a bool it went through
-                    // a byte of scratch, reloaded behind the tile's stores)
-                    const int last = __builtin_amdgcn_readfirstlane(has_agent(ri, it + 1) ? 0 : 1);
-                    rollout_tile<RNN, W2L, false, TAB, QOUT, true, SQ>(rollout_args(kra), e, sub, kk, ts + 1,
-                                                                       !first_sel || ri.reset, !first_sel, pass, key, s_scl,
-                                                                       sa, saw, s_h2, sw, hN, pass > 0,
-                                                                       HKeep{last});
-                } else {
-                    rollout_tile<RNN, W2L, false, TAB, QOUT, false, SQ>(rollout_args(kra), e, sub, kk, ts + 1, true, true, 0,
-                                                                        key, s_scl, sa, saw, s_h2, sw, hN, false,
-                                                                        HKeep{0});
+                // steps of the wave's parity (of the launch's step index: an odd G alternates)
+                for (int j = (sub + g0) & 1; j < gn; j += 2) {
+                    const int it = g0 + j;
+                    if (it < sf || (ASG_ROLLOUT_XSKIP & 256)) continue;  // the reset row's selection: no transition
+                    auto &ri = rollout_args(kra);
+                    const int k = ri.k0 + it - sf;
+                    const int ts = ri.ts0 + (k - ri.k0);
+                    // the tasks before step j's: the step before it in this group, else s_prev
+                    uint16_t *const pv = (j == 0 || it - 1 < sf) ? s_prev : s_hist + kPairRow * (j - 1);
+                    rollout_transition<TAB, SQ, true>(rollout_args(kra), e, k, ts, key, s_scl, s_cnt, s_hist + kPairRow * j,
+                                                      pv, s_sum(j));
+                }
+                t_last = moved ? s_hist[kPairRow * (gn - 1) + own] : s_prev[own];
+                t_next = s_hist[kPairRow * gn + own];
+            }
+            pair_barrier();  // the sums reach the fold; the history is free for the next group
+            if (active) {
+                const bool more = g0 + gn < nit;
+                if (lane < 32) {
+                    if (more) {
+                        s_prev[own] = t_last;
+                        s_hist[own] = t_next;
+                    } else {
+                        ra.prev[e * n + own] = t_last;
+                    }
+                }
+                if (trw && lane == 0) {
+                    // ret = (ret + S_j) + S_j+1 ...: the per-step code's additions, in its order
+                    double ret = *s_ret;
+                    for (int j = 0; j < gn; ++j)
+                        if (g0 + j >= sf && !(ASG_ROLLOUT_XSKIP & 256)) ret += *s_sum(j);
+                    *s_ret = ret;
+                    if (!more) ra.returns[e] = ret;
                 }
             }
-            if (agent) ++pass;
             wave_lds_fence();
-            pair_barrier();  // this pass's tasks reach the transition and the next tiles
         }
-        if (active && trw) {
-            ra.prev[e * n + lane] = s_prev[lane];
-            if (lane == 0) ra.returns[e] = *s_ret;
-        }
-        wave_lds_fence();
     }
 }
 
