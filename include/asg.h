@@ -401,7 +401,7 @@ int asg_mlp_agent_unroll_backward(const float *dh_q, const float *h_all, const f
                                   const float *W_r, int64_t N, int hidden, float *dh, float *dx1,
                                   void *hip_stream);
 /* asg_mlp_agent_unroll with the reference critics' agent-id inputs (modules/critics/ac.py:32-43):
- * W1 is [64][K + n] contiguous; row (t, env, agent) starts fc1 from b1 + W1[:, K + agent].
+ * W1 is [64][K + n] contiguous; row (t, env, agent) adds b1 + W1[:, K + agent] to fc1's products.
  * The [obs, eye(n)] concatenation is never built: x is the observation alone, as above, and the
  * same kernel source runs with the W1 row stride K + n (float4 loads of W1 when K % 4 == 0 and
  * (K + n) % 4 == 0).  The network is ACCritic's: W_r = fc2, W2 = fc3, n_out = m or 1.  Same

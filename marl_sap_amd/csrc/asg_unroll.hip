@@ -83,9 +83,11 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
         f32x4 x1[4];
         {
             const float *xr = xrow + (int64_t)ts * a.xs_t;
+            // the bias is added once, after the products: an accumulator that starts from it is
+            // rounded at the bias's magnitude by every MFMA (rows with |W1 x| << |b1|)
             f32x4 acc[4];
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) acc[mt] = ld4(a.b1 + 16 * mt + 4 * qd);
+            for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
             // two register buffers of kFc1G k-chunks each: one is refilled from L2 / HBM under the
             // MFMAs of the other (a single wave per SIMD has nothing else to hide that latency);
             // chunks past K load nothing (ldk) and are skipped
@@ -118,11 +120,15 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
                 mm(kc + kFc1G, xb, wb);
             }
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
+            for (int mt = 0; mt < 4; ++mt) {
+                const f32x4 b = ld4(a.b1 + 16 * mt + 4 * qd);
 #pragma unroll
-                for (int v = 0; v < 4; ++v) x1[mt][v] = fmaxf(acc[mt][v], 0.f);
+                for (int v = 0; v < 4; ++v) x1[mt][v] = fmaxf(acc[mt][v] + b[v], 0.f);
+            }
         }
-        // ---- GRUCell: r and z sum the input and hidden products in one accumulator ----
+        // ---- GRUCell: r and z sum the input and hidden products in one accumulator; the gate
+        // accumulators start from their biases (the gates' absolute floor covers that rounding),
+        // gh_n = W_hn h + b_hn, a plane of its own, gets its bias after the products ----
         f32x4 hn[4];
 #pragma unroll
         for (int hb = 0; hb < 4; ++hb) {
@@ -130,7 +136,7 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
             f32x4 gr = ld4(a.bih + u) + ld4(a.bhh + u);
             f32x4 gz = ld4(a.bih + kHid + u) + ld4(a.bhh + kHid + u);
             f32x4 gni = ld4(a.bih + 2 * kHid + u);
-            f32x4 gnh = ld4(a.bhh + 2 * kHid + u);
+            f32x4 gnh = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc) {
                 // keep the LDS reads of later chunks from being hoisted here (register pressure)
@@ -152,6 +158,7 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
                     gz = mfma4(wh[1][e], h[kc][e], gz);
                 }
             }
+            gnh = gnh + ld4(a.bhh + 2 * kHid + u);
             f32x4 rg, zg, ng;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
@@ -186,9 +193,9 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
         load_w2(0, wn);
         for (int c = 0; c < nct; ++c) {
             const int j0 = 16 * c + 4 * qd;
-            f32x4 acc;
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f}, b;  // the bias after the products, as in fc1
 #pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] = j0 + v < nout ? a.b2[j0 + v] : 0.f;
+            for (int v = 0; v < 4; ++v) b[v] = j0 + v < nout ? a.b2[j0 + v] : 0.f;
             f32x4 w[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) w[t] = wn[t];
@@ -197,6 +204,7 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc = mfma4(w[t][e], h[t][e], acc);
+            acc = acc + b;
             if (ok) {
                 if (qvec && j0 + 3 < nout) {
                     st4(qrow + j0, acc);

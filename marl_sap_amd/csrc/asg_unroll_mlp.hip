@@ -43,8 +43,8 @@ struct MlpFwdArgs {
 };
 
 // kIds: the reference critics' agent-id inputs (modules/critics/ac.py:32-43) -- W1 is [64][K + n]
-// and the one-hot block of row (t, env, agent) is the column gather W1[:, K + agent], added to
-// the bias before the K observation inputs are accumulated; the concatenation is never read.
+// and the one-hot block of row (t, env, agent) is the column gather W1[:, K + agent], added with
+// the bias after the K observation inputs are accumulated; the concatenation is never read.
 template <bool kIds>
 __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
     __shared__ float sWr[kHid * kWS];
@@ -73,16 +73,11 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
     // ---- fc1: x1^T = relu(W1 x^T + b1) ----
     f32x4 x1[4];
     {
+        // the bias (kIds: and the id column) is added once, after the products: an accumulator
+        // that starts from it is rounded at the bias's magnitude by every MFMA
         f32x4 acc[4];
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) acc[mt] = ld4(a.b1 + 16 * mt + 4 * qd);
-        if constexpr (kIds) {
-            const float *wid = a.W1 + K + ag;  // column K + agent of every W1 row
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) acc[mt][v] += wid[(int64_t)(16 * mt + 4 * qd + v) * ldw];
-        }
+        for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
         // two register buffers of kFc1G k-chunks each: one is refilled from L2 / HBM under the
         // MFMAs of the other; chunks past K load nothing (ldk) and are skipped
         f32x4 xa[kFc1G], wa[kFc1G][4], xb[kFc1G], wb[kFc1G][4];
@@ -114,24 +109,32 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
             mm(kc + kFc1G, xb, wb);
         }
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
+        for (int mt = 0; mt < 4; ++mt) {
+            f32x4 b = ld4(a.b1 + 16 * mt + 4 * qd);
+            if constexpr (kIds) {
+                const float *wid = a.W1 + K + ag;  // column K + agent of every W1 row
 #pragma unroll
-            for (int v = 0; v < 4; ++v) x1[mt][v] = fmaxf(acc[mt][v], 0.f);
+                for (int v = 0; v < 4; ++v) b[v] += wid[(int64_t)(16 * mt + 4 * qd + v) * ldw];
+            }
+#pragma unroll
+            for (int v = 0; v < 4; ++v) x1[mt][v] = fmaxf(acc[mt][v] + b[v], 0.f);
+        }
     }
     // ---- the middle layer: h^T = relu(W_r x1^T + b_r) ----
     f32x4 h[4];
 #pragma unroll
     for (int hb = 0; hb < 4; ++hb) {
         const int u = 16 * hb + 4 * qd;
-        f32x4 acc = ld4(a.br + u);
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
             const f32x4 w = ld4(sWr + (16 * hb + r) * kWS + 16 * kc + 4 * qd);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc = mfma4(w[e], x1[kc][e], acc);
         }
+        const f32x4 b = ld4(a.br + u);  // after the products, as in fc1
 #pragma unroll
-        for (int v = 0; v < 4; ++v) h[hb][v] = fmaxf(acc[v], 0.f);
+        for (int v = 0; v < 4; ++v) h[hb][v] = fmaxf(acc[v] + b[v], 0.f);
         if (ok) {
             st4(a.h_all + base + u, h[hb]);
             if (a.x1_save) st4(a.x1_save + base + u, x1[hb]);
@@ -150,9 +153,9 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
     load_w2(0, wn);
     for (int c = 0; c < nct; ++c) {
         const int j0 = 16 * c + 4 * qd;
-        f32x4 acc;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, b;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) acc[v] = j0 + v < nout ? a.b2[j0 + v] : 0.f;
+        for (int v = 0; v < 4; ++v) b[v] = j0 + v < nout ? a.b2[j0 + v] : 0.f;
         f32x4 w[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) w[t] = wn[t];
@@ -161,6 +164,7 @@ __global__ void __launch_bounds__(64 * kWaves) mlp_fwd_kernel(MlpFwdArgs a) {
         for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc = mfma4(w[t][e], h[t][e], acc);
+        acc = acc + b;
         if (ok) {
             if (qvec && j0 + 3 < nout) {
                 st4(qrow + j0, acc);
