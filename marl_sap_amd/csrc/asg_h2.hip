@@ -4,11 +4,13 @@
 //
 // This file holds the host side of both (input geometry, weight packing, LDS plan, launch)
 // and the kernels instantiated here: the agent kernel, the pack kernels and the rollout
-// kernel's Philox epsilon-greedy instances.  The device code lives in two headers: h2_tile.h
-// (the split-f16 arithmetic and one wave tile of the agent) and rollout_tile.h (the rollout
-// tile and kernel, shared with asg_rollout_tab.hip and asg_rollout_q.hip, which hold the
-// other instances).
-#include "rollout_tile.h"
+// kernel's Philox epsilon-greedy instances.  The device code lives in headers: h2_tile.h (the
+// split-f16 arithmetic and one wave tile of the agent) and, for the rollout kernel, one per
+// stage: rollout_args.h (arguments, LDS scratch layouts), rollout_env.h (env prologue,
+// transition), rollout_rows.h (whole-line row stores, compact table), rollout_tile.h (the
+// 32-agent tile) and rollout_kernel.h (env loops, kernel, instance launcher; shared with
+// asg_rollout_tab.hip and asg_rollout_q.hip, which hold the other instances).
+#include "rollout_kernel.h"
 
 #pragma clang fp contract(fast)
 
@@ -188,11 +190,17 @@ bool rollout_shape_ok(int n, int m, int L, int K) {
     return onehot_prefix_enabled() && h2_geom(K, m).prefix;
 }
 
+// the rollout kernel's LDS plan: the agent's image, then a scratch slot per wave (u32x4v units)
+static int64_t rollout_scratch_f4(int n, int m) {
+    return ((int64_t)rollout_scratch_bytes(n, m) * kH2Waves + 15) / 16;
+}
+static H2Lds rollout_lds_plan(const H2Geom &g, int n, int m, bool rnn) {
+    return h2_lds_plan(g, rnn, g.Pp / 32, rollout_scratch_f4(n, m));
+}
+
 int rollout_l2_slices(int n, int m, int L, int use_rnn) {
     if (!rollout_shape_ok(n, m, L, m * (L + 1))) return -1;
-    const H2Geom g = h2_geom(m * (L + 1), m);
-    const int64_t scr = ((int64_t)rollout_scratch_bytes(n, m) * kH2Waves + 15) / 16;
-    return h2_lds_plan(g, use_rnn != 0, g.Pp / 32, scr).l2_slices;
+    return rollout_lds_plan(h2_geom(m * (L + 1), m), n, m, use_rnn != 0).l2_slices;
 }
 
 // The pair mapping's group size G (steps whose transitions are deferred together): what the
@@ -201,9 +209,7 @@ int rollout_l2_slices(int n, int m, int L, int use_rnn) {
 // the pair mapping.
 int rollout_defer_steps(int n, int m, int L, int use_rnn) {
     if (n != 64 || m != 64 || !rollout_shape_ok(n, m, L, m * (L + 1))) return 0;
-    const H2Geom g = h2_geom(m * (L + 1), m);
-    const int64_t scr = ((int64_t)rollout_scratch_bytes(n, m) * kH2Waves + 15) / 16;
-    const H2Lds plan = h2_lds_plan(g, use_rnn != 0, g.Pp / 32, scr);
+    const H2Lds plan = rollout_lds_plan(h2_geom(m * (L + 1), m), n, m, use_rnn != 0);
     if (!plan.w2l) return 0;
     const int64_t room = (kH2LdsBytes - plan.scratch_off * 16) / (kH2Waves / 2);  // bytes per pair
     int G = kMaxDeferSteps;
@@ -282,8 +288,7 @@ hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, in
     ra.counter = counter;
     (void)row_base;  // = env_base * n (the selection keys by global row)
     ra.sel_err = err;
-    const int64_t scr_f4 = ((int64_t)rollout_scratch_bytes(st.n, st.m) * kH2Waves + 15) / 16;
-    const H2Lds plan = h2_lds_plan(g, rnn, g.Pp / 32, scr_f4);
+    const H2Lds plan = rollout_lds_plan(g, st.n, st.m, rnn);
     ra.w1_lds = plan.w1_lds;
     ra.w1_off = 0;  // 1 with the SQ64 instances (below)
     ra.scratch_off = plan.scratch_off;
@@ -294,21 +299,19 @@ hipError_t launch_rollout(const RolloutSlabs &sl, const EnvState &st, int ts, in
     lc.w2l = plan.w2l;
     lc.gen = st.m % 32 != 0 || st.n % 32 != 0;
     lc.sq64 = st.n == 64 && st.m == 64 && plan.w2l;
-    // agent passes of the launch (the kernel's has_agent): with two or more, the SQ64 selecting
+    // agent passes of the launch, as the kernel counts them: with two or more, the SQ64 selecting
     // instances keep the hidden state in registers between them (rollout_envs_pair); a single
     // pass has nothing to keep and runs one wave per env
     int passes = 0;
-    for (int it = 0, nit = steps + (select_first ? 1 : 0); it < nit; ++it) {
-        const int kk = k0 + it - (select_first ? 1 : 0) + 1;
-        passes += kk < st.T && (kk < ra.k1 || select_last);
-    }
+    const int sf = select_first ? 1 : 0, nit = steps + sf;
+    for (int it = 0; it < nit; ++it) passes += rollout_has_agent(it, nit, sf, ra.k0, ra.k1, ra.T, ra.select_last);
     lc.pair = lc.sq64 && !Q && passes >= 2;
     if (lc.pair) {
         // the pairs' scratch takes the wave slots' place, and the room behind them for the task history
         ra.defer = rollout_defer_steps(st.n, st.m, st.L, use_rnn);
         if (ra.defer < 1) return hipErrorInvalidValue;
         const int64_t pair_f4 = (int64_t)pair_scratch_bytes(ra.defer) * (kH2Waves / 2) / 16;
-        if (pair_f4 > scr_f4) lc.lds = (size_t)(plan.scratch_off + pair_f4) * 16;
+        if (pair_f4 > rollout_scratch_f4(st.n, st.m)) lc.lds = (size_t)(plan.scratch_off + pair_f4) * 16;
     }
     // envs in flight per workgroup: one per wave, or one per wave pair, whose scratch is the
     // pair's two wave slots of the plan above

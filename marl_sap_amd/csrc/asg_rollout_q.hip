@@ -1,6 +1,6 @@
 // asg_rollout_q.hip -- the rollout kernel instances that write the agent's Q rows instead of
 // selecting (asg_step_forward / asg_reset_forward, both benefit sources).
-#include "rollout_tile.h"
+#include "rollout_kernel.h"
 
 #pragma clang fp contract(fast)
 

@@ -1,6 +1,6 @@
 // asg_rollout_tab.hip -- the rollout kernel instances of the float64-table benefit modes
 // (MT19937 compat, injected sat_prox_mat), epsilon-greedy selection.
-#include "rollout_tile.h"
+#include "rollout_kernel.h"
 
 #pragma clang fp contract(fast)
 

@@ -1,7 +1,9 @@
 // h2_tile.h -- the RNNAgent forward on two-way-split f16 MFMAs (gfx950), device side: the
 // split primitives, the packed weight layout and LDS image, and one 32-row wave tile of the
 // agent (agent_rows_h2; its recurrent layer + fc2 + selection, h2_tail, is shared with the
-// rollout tile of rollout_tile.h).  The kernels that run it are in asg_h2.hip.
+// rollout tile of rollout_tile.h).  The kernels that run it are in asg_h2.hip; the rollout
+// kernel around its tile is in rollout_kernel.h (with rollout_args.h, rollout_env.h and
+// rollout_rows.h).
 //
 // Reference: modules/agents/rnn_agent.py:23-31 (fc1 -> ReLU -> GRUCell | Linear + ReLU ->
 // fc2), controllers/basic_controller.py:19-48 (select_actions), action_selectors/
