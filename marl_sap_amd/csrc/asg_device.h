@@ -76,9 +76,28 @@ __device__ __forceinline__ double mt_par_value(double2 p, int t) {
     return bump_value(p.y < 0.0 ? 10.0 : 1.0, p.x, bump_s2(__builtin_fabs(p.y)), t);
 }
 
-// purposes of Philox counters (counter.z); counter.w = episode
+// Purposes of Philox counters (counter.z), every one in this enum: two draw families under one
+// key never share a purpose, so no two of them read the same words.  counter.w is the env
+// handle's episode for the env draws and the selector's call counter for the selectors' draws.
+//   purpose             key                 counter (x, y)               words used
+//   1  kCtrScale        env_key             (task j, 0)                  x: task scale
+//   2  kCtrPair         --                  retired parameter layout
+//   3  kCtrSpread       --                  retired parameter layout
+//   4  kCtrPerm         env_key             (Fisher-Yates position, 0)   x: swap index
+//   5  kCtrAction       env_key             (agent i, step k)            x: random action
+//   6  kCtrSelect       selector key        (global row lo, hi)          x: explore, y: target
+//   7  kCtrSapNoise     env_key             (task j, row >> 2)           normal k -> row 4 (row >> 2) + k
+//   8  --               --                  retired (two pairs per call); not reused
+//   9  kCtrPair4        env_key             (pair >> 2, 0)               word pair & 3: bump parameters
+//   10 kCtrBidsNoise    env_key             (task j, row >> 2)           as kCtrSapNoise
+//   11 kCtrFiltTie      env_key             (task j >> 2, agent i)       word j & 3: tie uniform
+//   12 kCtrFiltGauss    env_key             (x >> 2, x >> 34), x = i m + j   normal x & 3
+//   13 kCtrFiltSoft     env_key             (agent i, 0)                 x: target outside the top M
+// (selector key = (seed lo, seed hi ^ 0x5bd1e995); the four normals of a call are Box-Muller's
+// cos / sin of (x, y) and of (z, w))
 enum : uint32_t { kCtrScale = 1u, kCtrPair = 2u, kCtrSpread = 3u, kCtrPerm = 4u, kCtrAction = 5u, kCtrSelect = 6u,
-                  kCtrSapNoise = 7u, kCtrPair2 = 8u, kCtrPair4 = 9u, kCtrBidsNoise = 10u };
+                  kCtrSapNoise = 7u, kCtrPair4 = 9u, kCtrBidsNoise = 10u, kCtrFiltTie = 11u, kCtrFiltGauss = 12u,
+                  kCtrFiltSoft = 13u };
 
 // "a beats b" in torch.max order: NaN wins, then larger value, then smaller index.
 // Branch-free (bitwise on the predicates) so it lowers to compares + v_cndmask.

@@ -27,8 +27,6 @@
 
 namespace asg {
 
-enum : uint32_t { kCtrFiltTie = 8u, kCtrFiltGauss = 9u, kCtrFiltSoft = 10u };
-
 // "a ranks before b" in torch.topk(largest) order: NaN first, then larger, then (our tie
 // rule) the smaller index
 template <class V>

@@ -19,7 +19,24 @@ every draw from (seed, global env index, episode, index) alone:
              for the global env g = env_index_base + e (as a uint64)
   counter    (index, second, purpose, episode); episode = resets of the handle so far
   purposes   1 task scale, 4 reset permutation, 5 random action, 9 bump parameters
-             (6 is the selector's, above; 7 / 10 the SAP / bids noise, not restated)
+             (6 is the selector's, above)
+
+The selectors' own draws use the same env key with the selector's seed and call counter in
+place of the env's seed and episode (PURPOSES below is the whole table):
+
+  7  SAP noise       counter (task j, row >> 2, 7, call): normal k of the call -> row 4 (row >> 2) + k;
+                     std = mean|Q| eps 2 per env (sap_stage.h)
+  10 bids noise      the same layout (asg_sap.hip, bids_select_kernel)
+  11 filtered tie    counter (j >> 2, agent i, 11, call): word j & 3, u = (w >> 8) 2^-24 (float32)
+  12 filtered Gauss  flat element x = i m + j: counter (x >> 2, x >> 34, 12, call), normal x & 3;
+                     std = float32(float32(mean|mat| eps) 2) per env
+  13 filtered soft   counter (agent i, 0, 13, call): target = (x (m - M)) >> 32 among the tasks
+                     outside the agent's top M, ascending
+
+The four normals of one call are Box-Muller's: u1 = ((w >> 8) + 1) 2^-24 from words x and z,
+u2 = (w >> 8) 2^-24 from words y and w, r = sqrt(-2 ln u1), then r cos(2 pi u2), r sin(2 pi u2)
+for (x, y) and for (z, w).  They are evaluated in float64 here; the device uses float32
+intrinsics, so a test compares them within a measured tolerance.
 
 Nothing under marl_sap_amd/ imports this module.
 """
@@ -32,11 +49,29 @@ _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
-K_CTR_SCALE = 1
-K_CTR_PERM = 4
-K_CTR_ACTION = 5
-K_CTR_SELECT = 6
-K_CTR_PAIR4 = 9
+# every draw family: (purpose word = counter word 2, the key it draws under)
+PURPOSES = {
+    "task_scale": (1, "env"),
+    "reset_perm": (4, "env"),
+    "random_action": (5, "env"),
+    "select": (6, "selector"),
+    "sap_noise": (7, "env"),
+    "bump_params": (9, "env"),
+    "bids_noise": (10, "env"),
+    "filtered_tie": (11, "env"),
+    "filtered_gauss": (12, "env"),
+    "filtered_soft": (13, "env"),
+}
+K_CTR_SCALE = PURPOSES["task_scale"][0]
+K_CTR_PERM = PURPOSES["reset_perm"][0]
+K_CTR_ACTION = PURPOSES["random_action"][0]
+K_CTR_SELECT = PURPOSES["select"][0]
+K_CTR_SAP_NOISE = PURPOSES["sap_noise"][0]
+K_CTR_PAIR4 = PURPOSES["bump_params"][0]
+K_CTR_BIDS_NOISE = PURPOSES["bids_noise"][0]
+K_CTR_FILT_TIE = PURPOSES["filtered_tie"][0]
+K_CTR_FILT_GAUSS = PURPOSES["filtered_gauss"][0]
+K_CTR_FILT_SOFT = PURPOSES["filtered_soft"][0]
 KEY_MIX = 0x85EBCA6B
 
 
@@ -71,6 +106,21 @@ def eps_greedy_draws(seed, global_rows, counter, epsilon, n_avail):
     explore = u < np.float32(epsilon) if epsilon > 0 else np.zeros(rows.shape, bool)
     target = ((y * np.asarray(n_avail, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)
     return explore, target
+
+
+def eps_greedy_actions(seed, row_base, counter, epsilon, avail, greedy):
+    """int64 [R]: the actions of the epsilon-greedy selection over R consecutive global rows
+    row_base, row_base + 1, ... (row = global env * n + agent).  avail [R, m] bool, greedy [R] =
+    the rows' non-exploring choice.  An exploring row with an available task takes the target-th
+    available task in index order, target = (y * n_avail) >> 32 with n_avail counted on that row."""
+    avail = np.asarray(avail, dtype=bool)
+    R = avail.shape[0]
+    rows = np.arange(R, dtype=np.uint64) + np.uint64(int(row_base))
+    n_avail = avail.sum(axis=1)
+    explore, target = eps_greedy_draws(seed, rows, counter, epsilon, n_avail)
+    rank = np.cumsum(avail, axis=1)  # 1-based rank of each available task among the row's available ones
+    pick = np.argmax(avail & (rank == (target + 1)[:, None]), axis=1)
+    return np.where(explore & (n_avail > 0), pick, np.asarray(greedy, dtype=np.int64)).astype(np.int64)
 
 
 # ---- the env draws -------------------------------------------------------------------------
@@ -194,3 +244,87 @@ def random_actions(seed, genvs, episode, n, m, T):
     """int64 [E, T, n]: agent i at step k takes (x m) >> 32 with x of counter (i, k, 5, episode)."""
     x = env_words(seed, genvs, np.arange(n)[None, :], np.arange(T)[:, None], K_CTR_ACTION, episode)[0]
     return ((x * np.uint64(m)) >> _S32).astype(np.int64)
+
+
+# ---- the selectors' draws ------------------------------------------------------------------
+_2M24 = 2.0 ** -24
+
+
+def normal_quads(words):
+    """float64 [..., 4]: the four Box-Muller normals of Philox calls whose words are (x, y, z, w)
+    (arrays of one shape): u1 = ((w >> 8) + 1) 2^-24 in (0, 1] from x and z, u2 = (w >> 8) 2^-24 in
+    [0, 1) from y and w (24-bit integers: exact), then sqrt(-2 ln u1) times cos / sin of 2 pi u2."""
+    x, y, z, w = (np.asarray(v, dtype=np.uint64) & _MASK for v in words)
+    s8, one = np.uint64(8), np.uint64(1)
+    u1 = np.stack([((x >> s8) + one), ((z >> s8) + one)], axis=-1).astype(np.float64) * _2M24
+    u2 = np.stack([y >> s8, w >> s8], axis=-1).astype(np.float64) * _2M24
+    r = np.sqrt(-2.0 * np.log(u1))
+    t = 2.0 * np.pi * u2
+    out = np.stack([r * np.cos(t), r * np.sin(t)], axis=-1)  # [..., pair (x y | z w), cos | sin]
+    return out.reshape(out.shape[:-2] + (4,))
+
+
+def _column_noise(seed, genvs, counter, n, m, purpose):
+    """float64 [E, n, m]: counter (task j, row >> 2, purpose, counter), normal k -> row 4 (row >> 2) + k."""
+    n4 = (n + 3) // 4
+    z = normal_quads(env_words(seed, genvs, np.arange(m)[None, :], np.arange(n4)[:, None], purpose, counter))
+    return np.moveaxis(z, -1, 2).reshape(z.shape[0], 4 * n4, m)[:, :n]  # [E, n4, m, 4] -> [E, n4, 4, m]
+
+
+def sap_noise(seed, genvs, counter, n, m):
+    """float64 [E, n, m]: the standard normals of the SAP selector's exploration noise."""
+    return _column_noise(seed, genvs, counter, n, m, K_CTR_SAP_NOISE)
+
+
+def bids_noise(seed, genvs, counter, n, m):
+    """float64 [E, n, m]: the standard normals of the bids noise."""
+    return _column_noise(seed, genvs, counter, n, m, K_CTR_BIDS_NOISE)
+
+
+def sap_std(q, eps):
+    """float64 [E]: the SAP noise's standard deviation mean|Q| eps 2 of each env, q [E, n, m]."""
+    return np.abs(np.asarray(q, dtype=np.float64)).mean(axis=(1, 2)) * float(eps) * 2.0
+
+
+def _flat_calls(seed, genvs, counter, second, count, purpose):
+    """The words of calls 0 .. ceil(count / 4) - 1, one element per word: uint64 [E, *second.shape, count]."""
+    calls = np.arange((count + 3) // 4, dtype=np.uint64)
+    second = np.asarray(second, dtype=np.uint64)
+    w = np.stack(env_words(seed, genvs, calls, second[..., None], purpose, counter), axis=-1)
+    return w.reshape(w.shape[:-2] + (-1,))[..., :count]
+
+
+def filtered_tie_u(seed, genvs, counter, n, m):
+    """float32 [E, n, m]: the tie uniforms: word j & 3 of counter (j >> 2, agent i, 11, counter),
+    u = (w >> 8) 2^-24."""
+    w = _flat_calls(seed, genvs, counter, np.arange(n), m, K_CTR_FILT_TIE)
+    return (w >> np.uint64(8)).astype(np.float32) * np.float32(_2M24)
+
+
+def filtered_gauss(seed, genvs, counter, n, m):
+    """float64 [E, n, m]: the standard normals of the filtered SAP selector's exploration noise:
+    flat element x = i m + j takes normal x & 3 of counter (x >> 2, x >> 34, 12, counter)."""
+    nm = n * m
+    calls = np.arange((nm + 3) // 4, dtype=np.uint64)
+    z = normal_quads(env_words(seed, genvs, calls & _MASK, calls >> _S32, K_CTR_FILT_GAUSS, counter))
+    return z.reshape(z.shape[0], -1)[:, :nm].reshape(-1, n, m)
+
+
+def filtered_std(mat, eps):
+    """float32 [E]: per env the float64 mean of |mat| over its n m entries, rounded to float32,
+    then (mean * eps) * 2 in float32."""
+    mean = np.abs(np.asarray(mat, dtype=np.float64)).mean(axis=(1, 2)).astype(np.float32)
+    return (mean * np.float32(eps)) * np.float32(2.0)
+
+
+def filtered_soft_target(seed, genvs, counter, n, m, M, topm):
+    """int64 [E, n]: the task a row picked at index M maps to: the target-th task in ascending
+    order outside the agent's top M (topm [E, n, M]), target = (x (m - M)) >> 32 with x of counter
+    (agent i, 0, 13, counter)."""
+    x = env_words(seed, genvs, np.arange(n), 0, K_CTR_FILT_SOFT, counter)[0]
+    target = ((x * np.uint64(m - M)) >> _S32).astype(np.int64)
+    # s_k - k tasks outside the top M lie below the k-th smallest top task s_k, so the target-th
+    # outside task has exactly those s_k with s_k - k <= target below it
+    s = np.sort(np.asarray(topm, dtype=np.int64), axis=-1)
+    below = ((s - np.arange(M)) <= target[..., None]).sum(axis=-1)
+    return target + below
