@@ -230,6 +230,25 @@ int asg_haa_select(const float *beta, const int64_t beta_strides[3], const int64
                    const int64_t prev_strides[2], int64_t B, int n, int m,
                    const double *T_trans_dev, double lambda_, float *col_out,
                    int32_t *status_out, void *hip_stream);
+/* Which solver instance a shape runs on (host only, no GPU call): cpl | storage << 8, where cpl
+ * is the working matrix's columns per lane (1, 2, 4, 8, 16 at up to 64, 128, 256, 512, 1024
+ * working columns) and storage says where the working matrix lives.  The launchers of
+ * asg_lsa_batched, asg_haa_select and the bids_as_actions step (asg_step on an m-task env) take
+ * their decision from the same functions.
+ *   asg_lsa_instance(dtype, nr, nc): the working matrix is [min(nr, nc)][max(nr, nc)]; float32 of
+ *     at most 64 working columns runs in registers, else LDS while sizeof(T) * nr * nc <= 48 KiB,
+ *     else in place from global memory.  ASG_E_INVALID_ARG for another dtype, max(nr, nc) > 1024,
+ *     or an empty shape (nr or nc <= 0: asg_lsa_batched launches nothing).
+ *   asg_haa_instance(n, m): registers at m <= 64, else the float32 beta in LDS while 4 * n * m <=
+ *     48 KiB, else in place.  ASG_E_INVALID_ARG where asg_haa_select rejects (n > m, m > 1024).
+ *   asg_bids_instance(n, m): registers at m <= 64, else LDS.  ASG_E_INVALID_ARG where asg_create
+ *     rejects a bids_as_actions env (n > m, n * m > 16384). */
+#define ASG_LSA_REGISTERS 0
+#define ASG_LSA_LDS 1
+#define ASG_LSA_GLOBAL 2
+int asg_lsa_instance(int dtype, int nr, int nc);
+int asg_haa_instance(int n, int m);
+int asg_bids_instance(int n, int m);
 
 /* SequentialAssignmentProblemSelector (sap_selectors.py:52-98) for n <= m <= 64, fused:
  * per env b, std = mean(|Q[b]|) * epsilon * 2 (float32), Q' = Q[b] + N(0, std^2) noise

@@ -47,7 +47,8 @@ EXPORTS = ["asg_abi_version", "asg_last_error", "asg_create", "asg_destroy", "as
            "asg_reset_forward", "asg_step_ex", "asg_step_forward_ex", "asg_bids_select_count",
            "asg_rnn_agent_unroll", "asg_rnn_agent_unroll_backward", "asg_mlp_agent_unroll",
            "asg_mlp_agent_unroll_backward", "asg_mlp_agent_unroll_ids", "asg_bids_log_prob", "asg_ppo_bids_loss",
-           "asg_nstep_returns"]
+           "asg_nstep_returns", "asg_lsa_instance", "asg_haa_instance", "asg_bids_instance"]
+ASG_LSA_REGISTERS, ASG_LSA_LDS, ASG_LSA_GLOBAL = 0, 1, 2
 ASG_PPO_ROWS_PER_GROUP = 16
 
 
@@ -180,6 +181,10 @@ def lib():
         L.asg_rollout_l2_slices.argtypes = [i32, i32, i32, i32]
         if hasattr(L, "asg_rollout_defer_steps"):  # absent from older A/B builds
             L.asg_rollout_defer_steps.argtypes = [i32, i32, i32, i32]
+        if hasattr(L, "asg_lsa_instance"):  # absent from older A/B builds
+            L.asg_lsa_instance.argtypes = [i32, i32, i32]
+            L.asg_haa_instance.argtypes = [i32, i32]
+            L.asg_bids_instance.argtypes = [i32, i32]
         L.asg_reset_rollout.argtypes = [vp, ctypes.POINTER(AsgBatchView), i32, i32, i32, vp, vp, vp, vp, vp, i32, i32,
                                         i32, vp, i64, vp, dbl, u64, u64, vp, vp]
         L.asg_sap_select_into.argtypes = [vp, i64p, i64, i32, i32, dbl, u64, u64, i64, vp, vp, vp, vp]

@@ -419,6 +419,22 @@ int asg_lsa_batched(const void *C, int dtype, const int64_t strides[3], int64_t 
     return e == hipSuccess ? ASG_OK : hip_fail(nullptr, e, "asg_lsa_batched");
 }
 
+int asg_lsa_instance(int dtype, int nr, int nc) {
+    if ((dtype != ASG_F32 && dtype != ASG_F64) || nr <= 0 || nc <= 0 || (nr > nc ? nr : nc) > 1024)
+        return ASG_E_INVALID_ARG;
+    return asg::lsa_instance(dtype, nr, nc);
+}
+
+int asg_haa_instance(int n, int m) {
+    if (n <= 0 || m <= 0 || n > m || m > 1024) return ASG_E_INVALID_ARG;
+    return asg::haa_instance(n, m);
+}
+
+int asg_bids_instance(int n, int m) {
+    if (n <= 0 || m <= 0 || n > m || (int64_t)n * m > 16384) return ASG_E_INVALID_ARG;
+    return asg::bids_instance(n, m);
+}
+
 int asg_haa_select(const float *beta, const int64_t beta_strides[3], const int64_t *prev,
                    const int64_t prev_strides[2], int64_t B, int n, int m, const double *T_trans_dev, double lambda_,
                    float *col_out, int32_t *status_out, void *hip_stream) {

@@ -279,14 +279,23 @@ static void launch_step_t(const Src &src, const asg_batch_view &bv, const EnvSta
         hipLaunchKernelGGL((step_kernel<1, Src, BIDS>), dim3(st.E), dim3(256), lds, s, src, bv, st, ts, k);
 }
 
+// cpl | storage << 8 of the bids_assign_kernel instance an (n, m) env runs (asg_bids_instance):
+// registers at m <= 64, else the bid matrix staged in LDS (n * m <= 16384, checked at create)
+int bids_instance(int n, int m) {
+    if (m <= 64) return 1 | ASG_LSA_REGISTERS << 8;
+    return (m <= 128 ? 2 : m <= 256 ? 4 : m <= 512 ? 8 : 16) | ASG_LSA_LDS << 8;
+}
+
 hipError_t launch_bids_assign(const asg_batch_view &bv, const EnvState &st, int ts, hipStream_t s) {
     const size_t lds = sizeof(float) * (size_t)st.n * st.m + 32;
     // bids matrices are at most 16384 entries (checked at create): m <= 16384 / n
-    if (st.m <= 64) hipLaunchKernelGGL(bids_assign_kernel<1>, dim3(st.E), dim3(64), lds, s, bv, st, ts);
-    else if (st.m <= 128) hipLaunchKernelGGL(bids_assign_kernel<2>, dim3(st.E), dim3(64), lds, s, bv, st, ts);
-    else if (st.m <= 256) hipLaunchKernelGGL(bids_assign_kernel<4>, dim3(st.E), dim3(64), lds, s, bv, st, ts);
-    else if (st.m <= 512) hipLaunchKernelGGL(bids_assign_kernel<8>, dim3(st.E), dim3(64), lds, s, bv, st, ts);
-    else hipLaunchKernelGGL(bids_assign_kernel<16>, dim3(st.E), dim3(64), lds, s, bv, st, ts);
+    switch (bids_instance(st.n, st.m) & 0xff) {
+        case 1: hipLaunchKernelGGL(bids_assign_kernel<1>, dim3(st.E), dim3(64), lds, s, bv, st, ts); break;
+        case 2: hipLaunchKernelGGL(bids_assign_kernel<2>, dim3(st.E), dim3(64), lds, s, bv, st, ts); break;
+        case 4: hipLaunchKernelGGL(bids_assign_kernel<4>, dim3(st.E), dim3(64), lds, s, bv, st, ts); break;
+        case 8: hipLaunchKernelGGL(bids_assign_kernel<8>, dim3(st.E), dim3(64), lds, s, bv, st, ts); break;
+        default: hipLaunchKernelGGL(bids_assign_kernel<16>, dim3(st.E), dim3(64), lds, s, bv, st, ts); break;
+    }
     return hipGetLastError();
 }
 

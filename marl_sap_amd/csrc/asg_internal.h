@@ -91,6 +91,11 @@ hipError_t launch_mt_seed(const EnvState &st, hipStream_t s);
 hipError_t launch_mt_advance(const EnvState &st, int64_t words, hipStream_t s);
 
 // LSA, beta_hat and the selectors (asg_lsa.hip, asg_sap.hip, asg_select.hip)
+// kernel instance of a shape, cpl | storage << 8 (ASG_LSA_REGISTERS / _LDS / _GLOBAL): the one
+// decision each launcher takes, exported as asg_lsa_instance / asg_haa_instance / asg_bids_instance
+int lsa_instance(int dtype, int nr, int nc);
+int haa_instance(int n, int m);
+int bids_instance(int n, int m);
 hipError_t launch_lsa_batched(const void *C, int dtype, const int64_t strides[3], int64_t B, int nr, int nc,
                               int maximize, int64_t *row_out, int64_t *col_out, int32_t *status_out,
                               hipStream_t s);

@@ -58,14 +58,33 @@ __device__ int solve_emit_cpl(const Acc &acc, int nr, int nc, Emit &emit) {
 // so the register budget of a 64-column problem is not that of a 1024-column one)
 static int cpl_for(int nc) { return nc <= 64 ? 1 : nc <= 128 ? 2 : nc <= 256 ? 4 : nc <= 512 ? 8 : 16; }
 
-#define ASG_DISPATCH_CPL(nc, LAUNCH) \
-    switch (cpl_for(nc)) {            \
+#define ASG_DISPATCH_CPL(cpl, LAUNCH) \
+    switch (cpl) {                    \
         case 1: LAUNCH(1); break;     \
         case 2: LAUNCH(2); break;     \
         case 4: LAUNCH(4); break;     \
         case 8: LAUNCH(8); break;     \
         default: LAUNCH(16); break;   \
     }
+
+// The kernel instance a shape runs on, cpl | storage << 8 (asg_lsa_instance / asg_haa_instance /
+// asg_bids_instance report it; the launchers below switch on nothing else).  Shapes are the
+// entry points' own (validated there).
+static int instance_code(int cpl, int storage) { return cpl | storage << 8; }
+
+int lsa_instance(int dtype, int nr0, int nc0) {
+    const int nr = nc0 < nr0 ? nc0 : nr0, nc = nc0 < nr0 ? nr0 : nc0;  // working orientation
+    const size_t elem = dtype == ASG_F32 ? sizeof(float) : sizeof(double);
+    const size_t cost_bytes = ((elem * (size_t)nr * nc + 15) / 16) * 16;
+    if (dtype == ASG_F32 && nc <= 64) return instance_code(1, ASG_LSA_REGISTERS);
+    return instance_code(cpl_for(nc), cost_bytes <= kLdsCostBudget ? ASG_LSA_LDS : ASG_LSA_GLOBAL);
+}
+
+int haa_instance(int n, int m) {
+    const size_t cost = ((sizeof(float) * (size_t)n * m + 15) / 16) * 16;
+    if (m <= 64) return instance_code(1, ASG_LSA_REGISTERS);
+    return instance_code(cpl_for(m), cost <= kLdsCostBudget ? ASG_LSA_LDS : ASG_LSA_GLOBAL);
+}
 
 // LDS carve: [cost (optional)][mark: nr0 ints]
 template <int CPL, typename IT, typename CT, bool LDS_COST>
@@ -145,20 +164,22 @@ static hipError_t launch_lsa_t(const IT *C, const int64_t st[3], int64_t B, int 
     const int nr = nc0 < nr0 ? nc0 : nr0, nc = nc0 < nr0 ? nr0 : nc0;
     const size_t cost_bytes = ((sizeof(CT) * (size_t)nr * nc + 15) / 16) * 16;
     const size_t scratch = lsa_scratch_bytes(nr0);
-    if (std::is_same<IT, float>::value && nc <= 64) {
+    const int inst = lsa_instance(std::is_same<IT, float>::value ? ASG_F32 : ASG_F64, nr0, nc0);
+    const int cpl = inst & 0xff, storage = inst >> 8;
+    if (storage == ASG_LSA_REGISTERS) {
         hipLaunchKernelGGL(lsa_reg_kernel, lsa_reg_grid(B), dim3(64 * kLsaWpb), 0, s, reinterpret_cast<const float *>(C),
                            st[0], st[1], st[2], nr0, nc0, maximize, row_out, col_out, status_out, B);
-    } else if (cost_bytes <= kLdsCostBudget) {
+    } else if (storage == ASG_LSA_LDS) {
 #define L_(CPL)                                                                                                   \
     hipLaunchKernelGGL((lsa_batched_kernel<CPL, IT, CT, true>), dim3(B), dim3(64), cost_bytes + scratch, s, C, \
                        st[0], st[1], st[2], nr0, nc0, maximize, row_out, col_out, status_out)
-        ASG_DISPATCH_CPL(nc, L_)
+        ASG_DISPATCH_CPL(cpl, L_)
 #undef L_
     } else {
 #define L_(CPL)                                                                                                 \
     hipLaunchKernelGGL((lsa_batched_kernel<CPL, IT, CT, false>), dim3(B), dim3(64), scratch, s, C, st[0], st[1], \
                        st[2], nr0, nc0, maximize, row_out, col_out, status_out)
-        ASG_DISPATCH_CPL(nc, L_)
+        ASG_DISPATCH_CPL(cpl, L_)
 #undef L_
     }
     return hipGetLastError();
@@ -320,20 +341,22 @@ hipError_t launch_haa_select(const float *beta, const int64_t bs[3], const int64
                              int32_t *status_out, hipStream_t s) {
     const size_t cost = ((sizeof(float) * (size_t)n * m + 15) / 16) * 16;
     const size_t rest = ((sizeof(int) * n + 15) / 16) * 16 + 64;
-    if (m <= 64) {
+    const int inst = haa_instance(n, m);
+    const int cpl = inst & 0xff, storage = inst >> 8;
+    if (storage == ASG_LSA_REGISTERS) {
         hipLaunchKernelGGL(haa_reg_kernel, lsa_reg_grid(B), dim3(64 * kLsaWpb), 0, s, beta, bs[0], bs[1], bs[2], prev,
                            ps[0], ps[1], n, m, T_trans, lambda_, col_out, status_out, B);
-    } else if (cost <= kLdsCostBudget) {
+    } else if (storage == ASG_LSA_LDS) {
 #define L_(CPL)                                                                                                 \
     hipLaunchKernelGGL((haa_select_kernel<CPL, true>), dim3(B), dim3(64), cost + rest, s, beta, bs[0], bs[1], bs[2], \
                        prev, ps[0], ps[1], n, m, T_trans, lambda_, col_out, status_out)
-        ASG_DISPATCH_CPL(m, L_)
+        ASG_DISPATCH_CPL(cpl, L_)
 #undef L_
     } else {
 #define L_(CPL)                                                                                                  \
     hipLaunchKernelGGL((haa_select_kernel<CPL, false>), dim3(B), dim3(64), rest, s, beta, bs[0], bs[1], bs[2], prev, \
                        ps[0], ps[1], n, m, T_trans, lambda_, col_out, status_out)
-        ASG_DISPATCH_CPL(m, L_)
+        ASG_DISPATCH_CPL(cpl, L_)
 #undef L_
     }
     return hipGetLastError();

@@ -126,6 +126,38 @@ def test_agent_pack_layout_without_gpu(L):
     assert L.asg_rnn_agent_packed_size(256, 32, 64, 1) < 0  # hidden must be 64
 
 
+def test_lsa_instances_without_gpu(L):
+    """The solver instance of a shape, cpl | storage << 8 (asg_lsa_instance / asg_haa_instance /
+    asg_bids_instance: the functions the launchers switch on).  Columns per lane 1, 2, 4, 8, 16 at
+    up to 64, 128, 256, 512, 1024 working columns; the working matrix in registers (float32, at most
+    64 columns), in LDS while sizeof(T) * nr * nc <= 48 KiB, else read in place."""
+    from marl_sap_amd import _lib
+    F32, F64 = _lib.ASG_F32, _lib.ASG_F64
+    REG, LDS, GLB = _lib.ASG_LSA_REGISTERS, _lib.ASG_LSA_LDS, _lib.ASG_LSA_GLOBAL
+    inst = lambda cpl, storage: cpl | storage << 8  # noqa: E731
+    for nc, cpl in [(64, 1), (65, 2), (128, 2), (129, 4), (256, 4), (257, 8), (512, 8), (513, 16), (1024, 16)]:
+        assert L.asg_lsa_instance(F64, 4, nc) == inst(cpl, LDS), nc
+        assert L.asg_lsa_instance(F32, 4, nc) == inst(cpl, REG if nc <= 64 else LDS), nc
+        assert L.asg_haa_instance(4, nc) == inst(cpl, REG if nc <= 64 else LDS), nc
+        assert L.asg_bids_instance(4, nc) == inst(cpl, REG if nc <= 64 else LDS), nc
+    assert L.asg_lsa_instance(F32, 96, 128) == inst(2, LDS) and L.asg_lsa_instance(F32, 97, 128) == inst(2, GLB)
+    assert L.asg_lsa_instance(F64, 48, 128) == inst(2, LDS) and L.asg_lsa_instance(F64, 49, 128) == inst(2, GLB)
+    assert L.asg_haa_instance(96, 128) == inst(2, LDS) and L.asg_haa_instance(97, 128) == inst(2, GLB)
+    assert L.asg_lsa_instance(F64, 64, 64) == inst(1, LDS)       # float64 has no register kernel
+    assert L.asg_lsa_instance(F32, 1024, 1024) == L.asg_lsa_instance(F64, 1024, 1024) == inst(16, GLB)
+    # transposed shapes classify by their working orientation [min][max]
+    assert L.asg_lsa_instance(F32, 64, 40) == L.asg_lsa_instance(F32, 40, 64) == inst(1, REG)
+    assert L.asg_lsa_instance(F32, 65, 40) == L.asg_lsa_instance(F32, 40, 65) == inst(2, LDS)
+    assert L.asg_lsa_instance(F32, 128, 97) == inst(2, GLB) and L.asg_lsa_instance(F32, 128, 96) == inst(2, LDS)
+    assert L.asg_lsa_instance(F64, 200, 70) == inst(4, GLB) and L.asg_lsa_instance(F64, 1000, 6) == inst(16, LDS)
+    # the bids env solves in LDS up to its documented maximum n * m = 16384
+    assert L.asg_bids_instance(128, 128) == inst(2, LDS) and L.asg_bids_instance(16, 1024) == inst(16, LDS)
+    E = _lib.ASG_E_INVALID_ARG
+    assert L.asg_lsa_instance(2, 4, 4) == L.asg_lsa_instance(F32, 4, 1025) == L.asg_lsa_instance(F64, 0, 4) == E
+    assert L.asg_haa_instance(5, 4) == L.asg_haa_instance(4, 1025) == E
+    assert L.asg_bids_instance(5, 4) == L.asg_bids_instance(129, 128) == L.asg_bids_instance(17, 1024) == E
+
+
 def test_rollout_l2_slices_without_gpu(L):
     """The fused rollout's LDS plan (asg_rollout_l2_slices): fc1 slices read through L2, -1 for
     shapes asg_rollout rejects (m < 16 or > 256, n > 256, L = 0)."""

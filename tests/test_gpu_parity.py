@@ -55,8 +55,13 @@ def test_lsa_golden(golden):
     ((256, 64, 48), "normal", np.float32), ((256, 48, 64), "normal", np.float32),
     ((64, 1, 64), "normal", np.float32), ((64, 64, 1), "normal", np.float32),
     ((256, 33, 40), "int2", np.float32), ((256, 64, 64), "corr", np.float32),
-    # float32 keys collide while float64 values differ (the exact selection path)
-    ((256, 64, 64), "near64", np.float64), ((256, 40, 64), "near32", np.float32)])
+    # near64: float32 keys collide while float64 values differ (the exact selection path of
+    # lsa_solve_wave<1>).  near32 does not reach that path: its reduced costs stay multiples of
+    # 2^-23 next to 1, so tied float32 keys are exactly equal float64 values (exact ties only;
+    # tests/test_lsa_instance_cases_host.py records it).  binade does, in the register solver: two
+    # binades make the reduced costs odd multiples of 2^-24 (tests/lsa_instance_cases.py)
+    ((256, 64, 64), "near64", np.float64), ((256, 40, 64), "near32", np.float32),
+    ((256, 40, 64), "binade", np.float32), ((256, 64, 64), "binade", np.float32)])
 def test_lsa_random_batches_vs_oracle(shape, kind, dtype):
     rng = np.random.RandomState(sum(shape) * 31 + len(kind))
     if kind == "normal":
@@ -67,6 +72,9 @@ def test_lsa_random_batches_vs_oracle(shape, kind, dtype):
         C = 1.0 + rng.randint(0, 1000, size=shape) * 2.0 ** -40
     elif kind == "near32":
         C = 1.0 + rng.randint(0, 8, size=shape) * 2.0 ** -23
+    elif kind == "binade":
+        base = rng.choice([1.0, 0.5], size=(shape[0], 1, shape[2]))
+        C = base + rng.randint(0, 8, size=shape) * (base * 2.0 ** -23)
     elif kind == "int3":
         C = rng.randint(0, 3, size=shape).astype(np.float64)
     elif kind == "int2":
