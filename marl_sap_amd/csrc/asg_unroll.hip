@@ -30,14 +30,13 @@ namespace {
 constexpr int kG = 3 * kHid;       // gate rows of W_ih / W_hh
 constexpr int kWS = kHid + 4;      // LDS row stride (floats) of W [192][64], forward
 constexpr int kWTS = kG + 4;       // LDS row stride (floats) of W^T [64][192], backward
-constexpr int kWaves = 4;          // waves per workgroup, 16 rows each
 constexpr int kFc1G = 4;           // fc1 k-chunks (of 16 inputs) per register buffer
 constexpr size_t kFwdLds = 2 * (size_t)kG * kWS * sizeof(float);     // 104,448 B
 constexpr size_t kBwdLds = 2 * (size_t)kHid * kWTS * sizeof(float);  // 100,352 B
 
 __device__ __forceinline__ float sigmoid_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-struct FwdArgs {
+struct FwdArgs {  // the entry fills it by position
     const float *x;
     int64_t xs_t, xs_e, xs_a;
     int T1;
@@ -60,17 +59,14 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
         st4(sWhh + row * kWS + c, ld4(a.Whh + row * kHid + c));
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 15, qd = lane >> 4;
-    const int64_t row0 = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * 16;
-    if (row0 >= a.R) return;  // whole wave idle
-    const int64_t row = row0 + r;
-    const bool ok = row < a.R;
-    const int64_t rc = ok ? row : 0;  // rows past R compute row 0 again and store nothing
+    const WaveRows wv(a.R);
+    if (wv.row0 >= a.R) return;  // whole wave idle
+    const int r = wv.r, qd = wv.qd;
+    const bool ok = wv.ok;
+    const int64_t rc = wv.rc;
     const int64_t env = rc / a.n;
     const int64_t ag = rc - env * a.n;
     const float *xrow = a.x + env * a.xs_e + ag * a.xs_a;
-    const int K = a.K, nk = (K + 15) / 16, nout = a.nout, nct = (nout + 15) / 16;
-    const bool xvec = a.xvec != 0, w1vec = a.w1vec != 0, qvec = (nout & 3) == 0;
     const int64_t plane = (int64_t)a.T1 * a.R * kHid;
 
     f32x4 h[4];
@@ -82,48 +78,13 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
         // ---- fc1: x1^T = relu(W1 x^T + b1) ----
         f32x4 x1[4];
         {
-            const float *xr = xrow + (int64_t)ts * a.xs_t;
-            // the bias is added once, after the products: an accumulator that starts from it is
-            // rounded at the bias's magnitude by every MFMA (rows with |W1 x| << |b1|)
-            f32x4 acc[4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            // two register buffers of kFc1G k-chunks each: one is refilled from L2 / HBM under the
-            // MFMAs of the other (a single wave per SIMD has nothing else to hide that latency);
-            // chunks past K load nothing (ldk) and are skipped
-            f32x4 xa[kFc1G], wa[kFc1G][4], xb[kFc1G], wb[kFc1G][4];
-            auto load = [&](int kc0, f32x4(&xv)[kFc1G], f32x4(&w)[kFc1G][4]) {
-#pragma unroll
-                for (int g = 0; g < kFc1G; ++g) {
-                    const int k = 16 * (kc0 + g) + 4 * qd;
-                    xv[g] = ldk(xr, k, K, xvec);
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) w[g][mt] = ldk(a.W1 + (int64_t)(16 * mt + r) * K, k, K, w1vec);
-                }
-                __builtin_amdgcn_sched_barrier(0);  // issue the loads here, not next to their use
-            };
-            auto mm = [&](int kc0, const f32x4(&xv)[kFc1G], const f32x4(&w)[kFc1G][4]) {
-#pragma unroll
-                for (int g = 0; g < kFc1G; ++g) {
-                    if (kc0 + g >= nk) break;  // wave-uniform
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-#pragma unroll
-                        for (int mt = 0; mt < 4; ++mt) acc[mt] = mfma4(w[g][mt][e], xv[g][e], acc[mt]);
-                }
-            };
-            load(0, xa, wa);
-            for (int kc = 0; kc < nk; kc += 2 * kFc1G) {
-                load(kc + kFc1G, xb, wb);
-                mm(kc, xa, wa);
-                load(kc + 2 * kFc1G, xa, wa);
-                mm(kc + kFc1G, xb, wb);
-            }
+            const Fc1Acc acc = fc1_products<kFc1G>(xrow + (int64_t)ts * a.xs_t, a.W1, a.K, a.K, a.xvec != 0,
+                                                   a.w1vec != 0, r, qd);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 const f32x4 b = ld4(a.b1 + 16 * mt + 4 * qd);
 #pragma unroll
-                for (int v = 0; v < 4; ++v) x1[mt][v] = fmaxf(acc[mt][v] + b[v], 0.f);
+                for (int v = 0; v < 4; ++v) x1[mt][v] = fmaxf(acc.t[mt][v] + b[v], 0.f);
             }
         }
         // ---- GRUCell: r and z sum the input and hidden products in one accumulator; the gate
@@ -180,45 +141,11 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_fwd_kernel(FwdArgs a) {
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) h[t] = hn[t];
-        // ---- fc2 one 16-output tile at a time: q^T = W2 h^T + b2 ----
-        float *qrow = a.q + ((int64_t)ts * a.R + rc) * nout;
-        // W2 fragments one tile ahead (tiles past n_out load nothing)
-        auto load_w2 = [&](int c, f32x4(&w)[4]) {
-            const int wr = 16 * c + r;  // W2 row of this lane's A fragment
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                w[t] = wr < nout ? ld4(a.W2 + (int64_t)wr * kHid + 16 * t + 4 * qd) : f32x4{0.f, 0.f, 0.f, 0.f};
-        };
-        f32x4 wn[4];
-        load_w2(0, wn);
-        for (int c = 0; c < nct; ++c) {
-            const int j0 = 16 * c + 4 * qd;
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f}, b;  // the bias after the products, as in fc1
-#pragma unroll
-            for (int v = 0; v < 4; ++v) b[v] = j0 + v < nout ? a.b2[j0 + v] : 0.f;
-            f32x4 w[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) w[t] = wn[t];
-            load_w2(c + 1, wn);
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = mfma4(w[t][e], h[t][e], acc);
-            acc = acc + b;
-            if (ok) {
-                if (qvec && j0 + 3 < nout) {
-                    st4(qrow + j0, acc);
-                } else {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (j0 + v < nout) qrow[j0 + v] = acc[v];
-                }
-            }
-        }
+        fc2_rows(a.W2, a.b2, a.nout, h, a.q + ((int64_t)ts * a.R + rc) * a.nout, ok, r, qd);
     }
 }
 
-struct BwdArgs {
+struct BwdArgs {  // the entry fills it by position
     const float *dhq, *dh_last, *save, *h_all, *h0;
     int64_t hs;
     const float *Wih, *Whh;
@@ -237,12 +164,11 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_bwd_kernel(BwdArgs a) {
         sThh[j * kWTS + k] = a.Whh[i];
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, r = lane & 15, qd = lane >> 4;
-    const int64_t row0 = ((int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6)) * 16;
-    if (row0 >= a.R) return;
-    const int64_t row = row0 + r;
-    const bool ok = row < a.R;
-    const int64_t rc = ok ? row : 0;
+    const WaveRows wv(a.R);
+    if (wv.row0 >= a.R) return;  // whole wave idle
+    const int r = wv.r, qd = wv.qd;
+    const bool ok = wv.ok;
+    const int64_t rc = wv.rc;
     const int64_t plane = (int64_t)a.T1 * a.R * kHid;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
@@ -329,16 +255,6 @@ __global__ void __launch_bounds__(64 * kWaves) unroll_bwd_kernel(BwdArgs a) {
     }
 }
 
-// the shape both entries take: the GRU agent at hidden 64
-const char *shape_error(int T1, int64_t R, int hidden, int n_out, int use_rnn) {
-    if (hidden != 64) return "hidden must be 64";
-    if (!use_rnn) return "use_rnn = 0 is not supported (the GRU agent only)";
-    if (n_out < 1 || n_out > 512) return "n_out must be in 1..512";
-    if (T1 < 1) return "T1 must be >= 1";
-    if (R < 1) return "needs at least one agent row";
-    return nullptr;
-}
-
 }  // namespace
 }  // namespace asg
 
@@ -348,47 +264,20 @@ extern "C" int asg_rnn_agent_unroll(const float *x, const int64_t x_strides[3], 
                                     const float *b_hh, const float *b2, int hidden, int n_out, int use_rnn, float *q,
                                     float *h_all, float *save, void *hip_stream) {
     using namespace asg;
+    const char *who = "asg_rnn_agent_unroll";
     const int64_t R = (B > 0 && n > 0) ? B * n : 0;
-    if (const char *m = shape_error(T1, R, hidden, n_out, use_rnn))
-        return fail((std::string("asg_rnn_agent_unroll: ") + m).c_str());
-    if (K < 1) return fail("asg_rnn_agent_unroll: K must be >= 1");
+    if (const char *m = seq_shape_error(hidden, use_rnn, n_out, T1, R, K)) return fail(who, m);
     if (!x || !x_strides || !W1 || !W_ih || !W_hh || !W2 || !b1 || !b_ih || !b_hh || !b2 || !q || !h_all)
-        return fail("asg_rnn_agent_unroll: NULL argument");
+        return fail(who, "NULL argument");
     if (!al(x, 4) || !al(W1, 4) || !al(q, 16) || !al(b2, 4) || !al(h0, 16) || h_stride % 4 != 0 || h_stride < 0 ||
         !al(W_ih, 16) || !al(W_hh, 16) || !al(W2, 16) || !al(b1, 16) || !al(b_ih, 16) || !al(b_hh, 16) ||
         !al(h_all, 16) || !al(save, 16))
-        return fail("asg_rnn_agent_unroll: misaligned pointer (16 B for h0, W_ih, W_hh, W2, b1, b_ih, b_hh, q, h_all, "
-                    "save; h_stride % 4 == 0)");
-    FwdArgs a;
-    a.x = x;
-    a.xs_t = x_strides[0];
-    a.xs_e = x_strides[1];
-    a.xs_a = x_strides[2];
-    a.T1 = T1;
-    a.R = R;
-    a.n = n;
-    a.K = K;
-    a.h0 = h0;
-    a.hs = h_stride;
-    a.W1 = W1;
-    a.b1 = b1;
-    a.Wih = W_ih;
-    a.bih = b_ih;
-    a.Whh = W_hh;
-    a.bhh = b_hh;
-    a.W2 = W2;
-    a.b2 = b2;
-    a.nout = n_out;
-    a.q = q;
-    a.h_all = h_all;
-    a.save = save;
-    a.xvec = K % 4 == 0 && al(x, 16) && ((a.xs_t | a.xs_e | a.xs_a) & 3) == 0;
-    a.w1vec = K % 4 == 0 && al(W1, 16);
-    const unsigned grid = (unsigned)((R + 16 * kWaves - 1) / (16 * kWaves));
-    hipLaunchKernelGGL(unroll_fwd_kernel, dim3(grid), dim3(64 * kWaves), kFwdLds, static_cast<hipStream_t>(hip_stream),
-                       a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ASG_OK : hip_fail(e, "asg_rnn_agent_unroll");
+        return fail(who, "misaligned pointer (16 B for h0, W_ih, W_hh, W2, b1, b_ih, b_hh, q, h_all, save; "
+                         "h_stride % 4 == 0)");
+    const int64_t *xs = x_strides;
+    const FwdArgs a = {x, xs[0], xs[1], xs[2], T1, R, n, K, h0, h_stride, W1, b1, W_ih, b_ih, W_hh, b_hh, W2, b2,
+                       n_out, q, h_all, save, vec_rows(x, K, xs[0], xs[1], xs[2]), vec_rows(W1, K, K)};
+    return launch_rows(who, unroll_fwd_kernel, R, kFwdLds, hip_stream, a);
 }
 
 extern "C" int asg_rnn_agent_unroll_backward(const float *dh_q, const float *dh_last, const float *save,
@@ -397,31 +286,13 @@ extern "C" int asg_rnn_agent_unroll_backward(const float *dh_q, const float *dh_
                                              int n_out, int use_rnn, float *dgi, float *dgh_n, float *dx1, float *dh0,
                                              void *hip_stream) {
     using namespace asg;
-    if (const char *m = shape_error(T1, R, hidden, n_out, use_rnn))
-        return fail((std::string("asg_rnn_agent_unroll_backward: ") + m).c_str());
+    const char *who = "asg_rnn_agent_unroll_backward";
+    if (const char *m = seq_shape_error(hidden, use_rnn, n_out, T1, R, 1)) return fail(who, m);
     if (!dh_q || !save || !h_all || !W_ih || !W_hh || !dgi || !dgh_n || !dx1)
-        return fail("asg_rnn_agent_unroll_backward: NULL argument");
+        return fail(who, "NULL argument");
     if (!al(dh_q, 16) || !al(dh_last, 16) || !al(save, 16) || !al(h_all, 16) || !al(h0, 16) || h_stride % 4 != 0 ||
         h_stride < 0 || !al(W_ih, 4) || !al(W_hh, 4) || !al(dgi, 16) || !al(dgh_n, 16) || !al(dx1, 16) || !al(dh0, 16))
-        return fail("asg_rnn_agent_unroll_backward: misaligned pointer (16 B; h_stride % 4 == 0)");
-    BwdArgs a;
-    a.dhq = dh_q;
-    a.dh_last = dh_last;
-    a.save = save;
-    a.h_all = h_all;
-    a.h0 = h0;
-    a.hs = h_stride;
-    a.Wih = W_ih;
-    a.Whh = W_hh;
-    a.T1 = T1;
-    a.R = R;
-    a.dgi = dgi;
-    a.dghn = dgh_n;
-    a.dx1 = dx1;
-    a.dh0 = dh0;
-    const unsigned grid = (unsigned)((R + 16 * kWaves - 1) / (16 * kWaves));
-    hipLaunchKernelGGL(unroll_bwd_kernel, dim3(grid), dim3(64 * kWaves), kBwdLds, static_cast<hipStream_t>(hip_stream),
-                       a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ASG_OK : hip_fail(e, "asg_rnn_agent_unroll_backward");
+        return fail(who, "misaligned pointer (16 B; h_stride % 4 == 0)");
+    const BwdArgs a = {dh_q, dh_last, save, h_all, h0, h_stride, W_ih, W_hh, T1, R, dgi, dgh_n, dx1, dh0};
+    return launch_rows(who, unroll_bwd_kernel, R, kBwdLds, hip_stream, a);
 }

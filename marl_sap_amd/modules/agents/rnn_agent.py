@@ -1,12 +1,15 @@
 """Shared-parameter agent network (reference: modules/agents/rnn_agent.py:7-31):
 fc1 -> ReLU -> GRUCell (use_rnn) or Linear+ReLU -> fc2, fp32, run in PyTorch-ROCm."""
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import _lib
+from .. import unroll as U
+
+# the unroll kernels' forward launches (modules/unroll.py); unroll() looks them up here per call
+_unroll_launch = U.gru_launch
+_mlp_launch = U.mlp_launch
 
 
 class RNNAgent(nn.Module):
@@ -51,139 +54,6 @@ class RNNAgent(nn.Module):
         return torch.stack(qs, dim=1), h
 
 
-class _GRUUnroll(torch.autograd.Function):
-    """asg_rnn_agent_unroll under autograd: the forward kernel saves x1, r, z, n and gh_n per
-    step, asg_rnn_agent_unroll_backward walks the recurrence back, and the parameter
-    gradients are GEMMs over the flattened T1 * R rows."""
-
-    @staticmethod
-    def forward(ctx, x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2):
-        q, h_all, save = _unroll_launch(x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2, True)
-        ctx.save_for_backward(x, h0, W1, Wih, Whh, W2, h_all, save)
-        B, T1, n, _ = x.shape
-        return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
-
-    @staticmethod
-    def backward(ctx, dq, dh_last):
-        x, h0, W1, Wih, Whh, W2, h_all, save = ctx.saved_tensors
-        B, T1, n, K = x.shape
-        R, H, n_out = B * n, Wih.shape[1], W2.shape[0]
-        N = T1 * R
-        dev = x.device
-        if dq is None:
-            dQ = torch.zeros((N, n_out), dtype=torch.float32, device=dev)
-        else:
-            dQ = dq.permute(1, 0, 2, 3).reshape(N, n_out).float().contiguous()
-        if dh_last is not None:
-            dh_last = dh_last.reshape(R, H).float().contiguous()
-        dh_q = dQ @ W2
-        dgi = torch.empty((N, 3 * H), dtype=torch.float32, device=dev)
-        dgh_n = torch.empty((N, H), dtype=torch.float32, device=dev)
-        dx1 = torch.empty((N, H), dtype=torch.float32, device=dev)
-        dh0 = torch.empty((R, H), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        h0k, hs = _h0_arg(h0, R, H)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().asg_rnn_agent_unroll_backward(
-                p(dh_q), p(dh_last), p(save), p(h_all), p(h0k), hs, p(Wih), p(Whh), T1, R, H, n_out, 1, p(dgi),
-                p(dgh_n), p(dx1), p(dh0), _lib.stream_ptr(dev)))
-        hf = h_all.view(N, H)
-        if h0k is None:
-            h_first = torch.zeros((R, H), dtype=torch.float32, device=dev)
-        else:
-            h_first = h0k.expand(R, H) if hs == 0 else h0k
-        h_prev = torch.cat([h_first, hf[:N - R]], dim=0)
-        dgh = torch.cat([dgi[:, :2 * H], dgh_n], dim=1)
-        xf = x.permute(1, 0, 2, 3).reshape(N, K)
-        if dh0 is not None and h0 is not None:
-            dh0 = dh0.sum(0, keepdim=True).view(h0.shape) if hs == 0 else dh0.view(h0.shape)
-        return (None, dh0, dx1.t() @ xf, dx1.sum(0), dgi.t() @ save[0].view(N, H), dgh.t() @ h_prev, dgi.sum(0),
-                dgh.sum(0), dQ.t() @ hf, dQ.sum(0))
-
-
-def _h0_arg(h0, R, H):
-    """h0 as the kernels take it: ([rows, H] tensor or None, row stride; 0 = one row broadcast)."""
-    if h0 is None:
-        return None, 0
-    if h0.numel() == H:
-        return h0.reshape(1, H).float().contiguous(), 0
-    h = h0.reshape(R, H)
-    if h.dtype != torch.float32 or h.stride(-1) != 1 or h.stride(0) % 4 != 0 or h.data_ptr() % 16 != 0:
-        h = h.float().contiguous()
-    return h, h.stride(0)
-
-
-def _unroll_launch(x, h0, W1, b1, Wih, Whh, bih, bhh, W2, b2, save):
-    B, T1, n, K = x.shape
-    R, H, n_out = B * n, Wih.shape[1], W2.shape[0]
-    dev = x.device
-    q = torch.empty((T1, R, n_out), dtype=torch.float32, device=dev)
-    h_all = torch.empty((T1, R, H), dtype=torch.float32, device=dev)
-    sv = torch.empty((5, T1, R, H), dtype=torch.float32, device=dev) if save else None
-    h0k, hs = _h0_arg(h0, R, H)
-    ws = [t.detach().contiguous() for t in (W1, Wih, Whh, W2, b1, bih, bhh, b2)]
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().asg_rnn_agent_unroll(
-            p(x), _lib.i64arr([x.stride(1), x.stride(0), x.stride(2)]), T1, B, n, K, p(h0k), hs, *[p(w) for w in ws],
-            H, n_out, 1, p(q), p(h_all), p(sv), _lib.stream_ptr(dev)))
-    return q, h_all, sv
-
-
-class _MLPUnroll(torch.autograd.Function):
-    """asg_mlp_agent_unroll under autograd (the Linear agent): the forward kernel saves x1 and
-    h of every row, asg_mlp_agent_unroll_backward takes the gradient back through the two ReLUs
-    and the middle layer, and the parameter gradients are GEMMs over the T1 * R rows."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, Wr, br, W2, b2):
-        q, h_all, x1 = _mlp_launch(x, W1, b1, Wr, br, W2, b2, True)
-        ctx.save_for_backward(x, Wr, W2, h_all, x1)
-        B, T1, n, _ = x.shape
-        return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
-
-    @staticmethod
-    def backward(ctx, dq, dh_last):
-        x, Wr, W2, h_all, x1 = ctx.saved_tensors
-        B, T1, n, K = x.shape
-        R, H, n_out = B * n, Wr.shape[1], W2.shape[0]
-        N = T1 * R
-        dev = x.device
-        if dq is None:
-            dQ = torch.zeros((N, n_out), dtype=torch.float32, device=dev)
-        else:
-            dQ = dq.permute(1, 0, 2, 3).reshape(N, n_out).float().contiguous()
-        dh_q = dQ @ W2
-        if dh_last is not None:
-            dh_q[N - R:] += dh_last.reshape(R, H).float()
-        dh = torch.empty((N, H), dtype=torch.float32, device=dev)
-        dx1 = torch.empty((N, H), dtype=torch.float32, device=dev)
-        Wrc = Wr.detach().contiguous()
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().asg_mlp_agent_unroll_backward(
-                p(dh_q), p(h_all), p(x1), p(Wrc), N, H, p(dh), p(dx1), _lib.stream_ptr(dev)))
-        xf = x.permute(1, 0, 2, 3).reshape(N, K)
-        return (None, dx1.t() @ xf, dx1.sum(0), dh.t() @ x1.view(N, H), dh.sum(0), dQ.t() @ h_all.view(N, H),
-                dQ.sum(0))
-
-
-def _mlp_launch(x, W1, b1, Wr, br, W2, b2, save):
-    B, T1, n, K = x.shape
-    R, H, n_out = B * n, Wr.shape[1], W2.shape[0]
-    dev = x.device
-    q = torch.empty((T1, R, n_out), dtype=torch.float32, device=dev)
-    h_all = torch.empty((T1, R, H), dtype=torch.float32, device=dev)
-    x1 = torch.empty((T1, R, H), dtype=torch.float32, device=dev) if save else None
-    ws = [t.detach().contiguous() for t in (W1, Wr, W2, b1, br, b2)]
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().asg_mlp_agent_unroll(
-            p(x), _lib.i64arr([x.stride(1), x.stride(0), x.stride(2)]), T1, B, n, K, *[p(w) for w in ws], H, n_out,
-            p(q), p(h_all), p(x1), _lib.stream_ptr(dev)))
-    return q, h_all, x1
-
-
 class RNNFusedAgent(RNNAgent):
     """RNNAgent with the same parameters / state_dict, whose inference forward (no autograd:
     the rollout's action selection) is one fused HIP kernel (asg_rnn_agent_forward: f32
@@ -221,7 +91,7 @@ class RNNFusedAgent(RNNAgent):
     def _common(self, x, h, hs):
         R, K = x.shape
         rnn = bool(self.args.use_rnn)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        p = U.ptr
         h_out = torch.empty((R, self.args.hidden_dim), dtype=torch.float32, device=x.device)
         args = [p(x), x.stride(0), R, K, p(h), hs, p(self._packed(K, x.device)), p(self.fc1.bias),
                 p(self.rnn.bias_ih if rnn else self.rnn.bias), p(self.rnn.bias_hh) if rnn else None,
@@ -270,7 +140,7 @@ class RNNFusedAgent(RNNAgent):
             hs = h.stride(0)
         if hs and h.shape[0] != R:
             raise ValueError(f"hidden state has {h.shape[0]} rows, the batch {R}")
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        p = U.ptr
         self._h_keep = h  # alive until the kernel has read it (stream order)
         h_out = torch.empty((R, H), dtype=torch.float32, device=device)
         rnn = bool(self.args.use_rnn)
@@ -301,7 +171,7 @@ class RNNFusedAgent(RNNAgent):
         ps = (self.fc1.weight, self.fc1.bias, self.rnn.weight_ih, self.rnn.weight_hh, self.rnn.bias_ih,
               self.rnn.bias_hh, self.fc2.weight, self.fc2.bias)
         if torch.is_grad_enabled() and (any(w.requires_grad for w in ps) or (h0 is not None and h0.requires_grad)):
-            return _GRUUnroll.apply(x, h0, *ps)
+            return U._GRUUnroll.apply(_unroll_launch, x, h0, *ps)
         q, h_all, _ = _unroll_launch(x, h0, *ps, False)
         return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
 
@@ -312,7 +182,7 @@ class RNNFusedAgent(RNNAgent):
         B, T1, n, _ = x.shape
         ps = (self.fc1.weight, self.fc1.bias, self.rnn.weight, self.rnn.bias, self.fc2.weight, self.fc2.bias)
         if torch.is_grad_enabled() and any(w.requires_grad for w in ps):
-            return _MLPUnroll.apply(x, *ps)
+            return U._MLPUnroll.apply(_mlp_launch, False, x, *ps)
         q, h_all, _ = _mlp_launch(x, *ps, False)
         return q.view(T1, B, n, -1).permute(1, 0, 2, 3), h_all[T1 - 1]
 
@@ -330,7 +200,7 @@ class RNNFusedAgent(RNNAgent):
             nbytes = L.asg_rnn_agent_packed_size(K, self.args.hidden_dim, self.n_out, int(bool(rnn)))
             _lib.check(int(nbytes) if nbytes < 0 else 0)
             buf = torch.empty(int(nbytes) // 4, dtype=torch.float32, device=device)
-            p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+            p = U.ptr
             _lib.check(L.asg_rnn_agent_pack(p(ws[0]), p(ws[1]), p(ws[2]), p(ws[3]), K, self.args.hidden_dim,
                                             self.n_out, int(bool(rnn)), p(buf), _lib.stream_ptr(device)))
             self._pack_buf, self._pack_key = buf, key

@@ -8,64 +8,17 @@ fc1.weight: x1 = relu(W1[:, :K] obs + W1[:, K + agent] + b1).  On a GPU (hidden 
 asg_mlp_agent_unroll_ids and the sequential part of its backward pass one launch of
 asg_mlp_agent_unroll_backward; the [obs, eye(n)] concatenation -- a copy of the whole observation
 buffer -- is never built.  Elsewhere it is the plain PyTorch module."""
-import ctypes
+import functools
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ... import _lib
+from .. import unroll as U
 
 
-class _MLPUnrollIds(torch.autograd.Function):
-    """asg_mlp_agent_unroll_ids under autograd, _MLPUnroll with the agent-id block of W1: the
-    forward kernel saves x1 and h of every row, asg_mlp_agent_unroll_backward takes the gradient
-    back through the two ReLUs and the middle layer, and the parameter gradients are GEMMs over
-    the T1 * R rows (the id block's: the per-agent sums of dx1).  Returns q [T1, R, n_out]."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, Wr, br, W2, b2):
-        q, h_all, x1 = _ids_launch(x, W1, b1, Wr, br, W2, b2, True)
-        ctx.save_for_backward(x, Wr, W2, h_all, x1)
-        return q
-
-    @staticmethod
-    def backward(ctx, dq):
-        x, Wr, W2, h_all, x1 = ctx.saved_tensors
-        B, T1, n, K = x.shape
-        R, H, n_out = B * n, Wr.shape[1], W2.shape[0]
-        N = T1 * R
-        dev = x.device
-        dQ = dq.reshape(N, n_out).float().contiguous()
-        dh_q = dQ @ W2
-        dh = torch.empty((N, H), dtype=torch.float32, device=dev)
-        dx1 = torch.empty((N, H), dtype=torch.float32, device=dev)
-        Wrc = Wr.detach().contiguous()
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().asg_mlp_agent_unroll_backward(
-                p(dh_q), p(h_all), p(x1), p(Wrc), N, H, p(dh), p(dx1), _lib.stream_ptr(dev)))
-        xf = x.permute(1, 0, 2, 3).reshape(N, K)
-        dW1 = torch.cat([dx1.t() @ xf, dx1.view(T1, B, n, H).sum((0, 1)).t()], dim=1)
-        return (None, dW1, dx1.sum(0), dh.t() @ x1.view(N, H), dh.sum(0), dQ.t() @ h_all.view(N, H), dQ.sum(0))
-
-
-def _ids_launch(x, W1, b1, Wr, br, W2, b2, save):
-    """One asg_mlp_agent_unroll_ids launch on x [B, T1, n, K] (any batch / time / agent strides):
-    q [T1, R, n_out], h [T1, R, 64] and, with save, x1 [T1, R, 64]."""
-    B, T1, n, K = x.shape
-    R, H, n_out = B * n, Wr.shape[1], W2.shape[0]
-    dev = x.device
-    q = torch.empty((T1, R, n_out), dtype=torch.float32, device=dev)
-    h_all = torch.empty((T1, R, H), dtype=torch.float32, device=dev)
-    x1 = torch.empty((T1, R, H), dtype=torch.float32, device=dev) if save else None
-    ws = [t.detach().contiguous() for t in (W1, Wr, W2, b1, br, b2)]
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().asg_mlp_agent_unroll_ids(
-            p(x), _lib.i64arr([x.stride(1), x.stride(0), x.stride(2)]), T1, B, n, K, *[p(w) for w in ws], H, n_out,
-            p(q), p(h_all), p(x1), _lib.stream_ptr(dev)))
-    return q, h_all, x1
+# one asg_mlp_agent_unroll_ids launch (modules/unroll.py); _rows_fused looks it up here per call
+_ids_launch = functools.partial(U.mlp_launch, ids=True)
 
 
 class ACCritic(nn.Module):
@@ -122,7 +75,7 @@ class ACCritic(nn.Module):
         x = x.detach()  # observations are data: no gradient flows into them
         ps = (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.fc3.weight, self.fc3.bias)
         if torch.is_grad_enabled() and any(w.requires_grad for w in ps):
-            return _MLPUnrollIds.apply(x, *ps)
+            return U._MLPUnroll.apply(_ids_launch, True, x, *ps)
         return _ids_launch(x, *ps, False)[0]
 
     def _get_input_shape(self, scheme):

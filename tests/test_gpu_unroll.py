@@ -21,6 +21,10 @@ NAMES = ["fc1.weight", "fc1.bias", "rnn.weight_ih", "rnn.weight_hh", "rnn.bias_i
 # across waves with K % 4 != 0; the aligned split-f16 shape; n_out > 256; the workload's depth
 SHAPES = [(1, 3, 5, 20, 7), (4, 3, 5, 20, 7), (5, 2, 37, 70, 20), (3, 4, 16, 256, 64), (2, 1, 20, 490, 450),
           (21, 2, 8, 64, 16)]
+# the edges of fc1's two-buffer pipeline (4 chunks of 16 inputs per buffer): nk = ceil(K / 16) = 1 (the
+# first buffer alone, partly filled), 8 (both buffers full, one round), 9 (one chunk into a second
+# round), and 9 with K % 4 != 0 (scalar loads, a 2-wide last chunk)
+PIPELINE_K = [16, 128, 144, 130]
 
 
 def _loop(agent, x, h0):
@@ -69,6 +73,16 @@ def _run(fn, agent, x, h0, wq, wh):
 @pytest.mark.parametrize("time_major", [False, True])
 @pytest.mark.parametrize("T1,B,n,K,m", SHAPES)
 def test_unroll_forward_and_gradients_match_float64(T1, B, n, K, m, time_major, dense_h0):
+    _check_against_float64(T1, B, n, K, m, time_major, dense_h0)
+
+
+@pytest.mark.parametrize("K", PIPELINE_K)
+def test_unroll_at_the_fc1_pipeline_edges(K):
+    """R = 17: one full 16-row tile and a one-row tile; n_out = 5: one partial fc2 tile, scalar stores."""
+    _check_against_float64(2, 1, 17, K, 5, False, True)
+
+
+def _check_against_float64(T1, B, n, K, m, time_major, dense_h0):
     ref, fused, ref64, x, h0, wq, wh = _make(T1, B, n, K, m, time_major, dense_h0, T1 * 100 + K)
     d = lambda t: None if t is None else t.double()  # noqa: E731
     q64, h64, g64 = _run(_loop, ref64, x.double(), d(h0), wq.double(), wh.double())

@@ -24,6 +24,13 @@ NAMES = ["fc1.weight", "fc1.bias", "rnn.weight", "rnn.bias", "fc2.weight", "fc2.
 SEEDS = {(1, 3, 5, 20, 7): 0, (4, 3, 5, 20, 7): 0, (5, 2, 37, 70, 20): 16, (3, 4, 16, 256, 64): 1,
          (2, 1, 20, 490, 450): 0}
 SHAPES = list(SEEDS)
+# the edges of fc1's two-buffer pipeline (2 chunks of 16 inputs per buffer): nk = ceil(K / 16) = 1 (the
+# first buffer alone, partly filled), 3 (one chunk into the second buffer), 4 (both buffers full, one
+# round), and 3 with K % 4 != 0 (scalar loads, a 1-wide last group); R = 17, N = 34 flattened rows:
+# two full 16-row tiles, one across the time boundary, and a two-row tile; n_out = 5: one partial
+# fc2 tile, scalar stores
+PIPELINE_SEEDS = {(2, 1, 17, 3, 5): 0, (2, 1, 17, 48, 5): 0, (2, 1, 17, 64, 5): 0, (2, 1, 17, 37, 5): 0}
+SEEDS.update(PIPELINE_SEEDS)
 RELU_MARGIN = 1e-5
 
 
@@ -100,6 +107,15 @@ def _layout(x, time_major):
 @pytest.mark.parametrize("time_major", [False, True])
 @pytest.mark.parametrize("shape", SHAPES)
 def test_mlp_unroll_forward_and_gradients_match_float64(shape, time_major):
+    _check_against_float64(shape, time_major)
+
+
+@pytest.mark.parametrize("shape", list(PIPELINE_SEEDS))
+def test_mlp_unroll_at_the_fc1_pipeline_edges(shape):
+    _check_against_float64(shape, False)
+
+
+def _check_against_float64(shape, time_major):
     T1, B, n, K, m = shape
     state, x, wq, wh, (q64, h64, g64), margin = _case(shape)
     # the condition on the inputs: no ReLU can flip between float64 and float32

@@ -3,7 +3,7 @@ _backward) outside default-init scales, per row class, against float64: the case
 tolerances of tests/unroll_scale_cases.py (their preconditions, and a CPU model showing that a
 correct kernel has room: tests/test_unroll_scale_cases_host.py).
 
-The ABI entries are called directly, as rnn_agent.py and ac.py call them, on output buffers the
+The ABI entries are called directly, as modules/unroll.py calls them, on output buffers the
 test owns: each has 64 extra rows and is pre-filled with a NaN payload no result can equal; after
 the launch the tail must be untouched and no live element may still hold the pattern.
 

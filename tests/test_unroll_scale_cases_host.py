@@ -12,6 +12,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from marl_sap_amd.modules.agents import RNNAgent  # noqa: E402
+from marl_sap_amd.modules.unroll import gru_param_grads, mlp_param_grads  # noqa: E402
 from tests import unroll_scale_cases as C  # noqa: E402
 from tests.cont_ppo_ref import RefCritic  # noqa: E402
 
@@ -64,10 +65,17 @@ def test_references_are_the_modules_in_float64(args):
     _close(p["q"], q.detach())
 
 
+# the order of the shipped functions' results: the modules' parameter order
+PARAMS = {"gru": ("fc1.weight", "fc1.bias", "rnn.weight_ih", "rnn.weight_hh", "rnn.bias_ih", "rnn.bias_hh",
+                  "fc2.weight", "fc2.bias"),
+          "mlp": ("fc1.weight", "fc1.bias", "rnn.weight", "rnn.bias", "fc2.weight", "fc2.bias"),
+          "ids": ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias")}
+
+
 @pytest.mark.parametrize("args", FWD, ids=str)
 def test_backward_references_are_float64_autograd(args):
-    """gru_bptt / mlp_bwd assembled into parameter gradients the way _GRUUnroll.backward,
-    _MLPUnroll.backward and _MLPUnrollIds.backward do, against autograd of the module."""
+    """gru_bptt / mlp_bwd assembled into parameter gradients by the functions the autograd wrappers
+    call (modules/unroll.py: gru_param_grads, mlp_param_grads), against autograd of the module."""
     c = C.case(*args)
     g = torch.Generator().manual_seed(11)
     wq = torch.randn((c.T1, c.R, c.m), generator=g, dtype=torch.float64)
@@ -83,15 +91,12 @@ def test_backward_references_are_float64_autograd(args):
     W2 = c.sd[nm[3 if c.kind == "gru" else 2]].double()
     dQ = wq.reshape(N, c.m)
     dh_q = (dQ @ W2).view(c.T1, c.R, H)
-    xf = C.x_rows(c).double().reshape(N, c.K)
+    x = c.x.double()
     if c.kind == "gru":
         p, h_prev = C.gru_chain(c, torch.float64)
         b = C.gru_bptt(p, h_prev, dh_q, wh, c.sd["rnn.weight_ih"], c.sd["rnn.weight_hh"], torch.float64)
-        dgi, dx1 = b["dgi"].reshape(N, 3 * H), b["dx1"].reshape(N, H)
-        dgh = torch.cat([dgi[:, :2 * H], b["dgh_n"].reshape(N, H)], dim=1)
-        got = {"fc1.weight": dx1.t() @ xf, "fc1.bias": dx1.sum(0), "rnn.weight_ih": dgi.t() @ p["x1"].reshape(N, H),
-               "rnn.weight_hh": dgh.t() @ h_prev.reshape(N, H), "rnn.bias_ih": dgi.sum(0), "rnn.bias_hh": dgh.sum(0),
-               "fc2.weight": dQ.t() @ p["h"].reshape(N, H), "fc2.bias": dQ.sum(0)}
+        got = gru_param_grads(x, h_prev[0], p["x1"], p["h"], b["dgi"].reshape(N, 3 * H), b["dgh_n"].reshape(N, H),
+                              b["dx1"].reshape(N, H), dQ)
         _close(b["dh0"], h0.grad, 1e-11)
     else:
         p = C.forward_reference(c, torch.float64)
@@ -99,12 +104,9 @@ def test_backward_references_are_float64_autograd(args):
         if c.kind == "mlp":
             dh_q[-1] += wh
         b = C.mlp_bwd(dh_q, p["h"], p["x1"], c.sd[nm[1]], torch.float64)
-        dh, dx1 = b["dh"].reshape(N, H), b["dx1"].reshape(N, H)
-        dW1 = dx1.t() @ xf
-        if c.kind == "ids":
-            dW1 = torch.cat([dW1, dx1.view(c.T1, c.B, c.n, H).sum((0, 1)).t()], dim=1)
-        got = dict(zip(nm, (dW1, dh.t() @ p["x1"].reshape(N, H), dQ.t() @ p["h"].reshape(N, H), dx1.sum(0), dh.sum(0),
-                            dQ.sum(0))))
+        got = mlp_param_grads(x, p["x1"], p["h"], b["dh"].reshape(N, H), b["dx1"].reshape(N, H), dQ, c.kind == "ids")
+    assert len(got) == len(PARAMS[c.kind])
+    got = dict(zip(PARAMS[c.kind], got))
     assert set(got) == set(want)
     for k in want:
         _close(got[k], want[k], 1e-11)
